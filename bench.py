@@ -1,15 +1,24 @@
 """Headline benchmark: brute-force top-100 retrieval throughput (queries/sec).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warm-up and K timed steps, writes the outputs of the last timed
+step if asked to and prints the result line; everything else this file measures or checks (marked
+"--full" below) runs only with `--full`.
+
+--dump-outputs DIR: after the timed steps, what the timed step returned in its last step is written
+as DIR/<name>.npy (float32, or float64 for integer outputs: exact), at most 64 MB in all (a fixed,
+seeded sample of the rows of a larger output).  Inputs are generated from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 
 N = 1 (BASELINE.json configs[1], the configuration the metric is quoted on): synthetic
 1M-item x dim-64 corpus, batch of 8192 queries, exact top-100 (`BruteForce.call`, reference
 layers/factorized_top_k.py:586-607), inputs resident in HBM before the timed region.  Returned
 scores and indices are those of the float32 fma chain (bit-identical to the all-f32 path); the
 default path FILTERS with fp16 MFMA scores under a rigorous error bound and re-scores the
-survivors exactly.  A "step" is one `BruteForce` call on the batch.  The same
-line also carries `scale_workload`: the single-GPU rate on the 100M x 64 corpus, the N = 1 point
-of the strong-scaling configuration below.
+survivors exactly.  A "step" is one `BruteForce` call on the batch.  With --full
+the same line also carries `scale_workload`: the single-GPU rate on the 100M x 64 corpus, the N = 1
+point of the strong-scaling configuration below.
 
 N > 1 (north_star: ">= 6x top-K throughput at 8 GPUs vs 1 GPU on a 100M x 64 corpus"):
 STRONG scaling -- the 100M x 64 corpus is row-sharded over the N ranks (one process per GPU,
@@ -27,7 +36,9 @@ events on the launch stream -> `step_ms_median/p10/p90`.  While the K steps run 
 brackets each scan launch with HIP events on its stream (`tfrs_profile_enable`; two event
 records per launch inside the timed region -- conservative for `value`): `roofline` is the
 kernel the step spends most time in, priced with its ALGORITHMIC flop 2*B*N*D against the
-dense 16-bit MFMA peak.  N = 1 only: `cpu_baseline` (oracle restatement on the host cores),
+dense 16-bit MFMA peak (with --full, also against the box's own ceilings measured after the timed
+region).  --full, N > 1: `single_gpu_same_workload` (the same workload on rank 0 alone) and the
+speed-up over it.  --full, N = 1 only: `cpu_baseline` (oracle restatement on the host cores),
 `secondary` (train steps/sec of `Model.fit` with its own roofline + cpu_baseline), `gather` (embedding
 gather GB/s at BASELINE configs[3] shapes), `streaming` (Streaming over a dataset of blocks, one GPU's
 shard of configs[2]) and `config_legs` (bench_legs.py: fused Cross, DotInteraction, segment-sum, sparse
@@ -73,7 +84,15 @@ def parse_args():
   ap.add_argument("--no-streaming", action="store_true")
   ap.add_argument("--no-config-legs", action="store_true")
   ap.add_argument("--no-single-gpu-reference", action="store_true")
-  return ap.parse_args()
+  ap.add_argument("--full", action="store_true",
+                  help="besides the headline steps, run every other measurement and check of the line (the --no-* "
+                       "options switch single ones off)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write the outputs of the last timed step as DIR/<name>.npy")
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
+  return args
 
 
 def respawn_under_torchrun(args) -> None:
@@ -177,6 +196,36 @@ def emit(result: dict) -> None:
   print("bench_detail: " + json.dumps(result), flush=True)
   sys.stdout.flush()
   print(bench_compact.dumps(result), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_rows(t: "torch.Tensor", n: int, seed: int) -> "torch.Tensor":
+  """A fixed, seeded sample of n rows (first dimension, drawn with replacement) of t, in ascending row order; all of
+  t if it has <= n rows."""
+  if t.shape[0] <= n:
+    return t
+  g = torch.Generator(device="cpu").manual_seed(seed)
+  rows = torch.randint(0, t.shape[0], (n,), generator=g).sort().values
+  return t[rows.to(t.device)]
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+  """--dump-outputs: name -> tensor of the last timed step, written as DIR/<name>.npy; float32 for floating-point
+  outputs of up to 32 bits, float64 otherwise (integer rows and ids are exact in float64)."""
+  import numpy as np
+  host = {}
+  for name, t in arrays.items():
+    t = t.detach()
+    t = t.float() if t.is_floating_point() and t.element_size() <= 4 else t.double()
+    host[name] = t.cpu().numpy()
+  total = sum(a.nbytes for a in host.values())
+  if total > DUMP_LIMIT_BYTES:
+    raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+  os.makedirs(dirname, exist_ok=True)
+  for name, a in host.items():
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def percentiles(xs):
@@ -487,7 +536,7 @@ def streaming_metric(dev) -> dict:
 
 def timed_region(fn, steps: int, warmup: int, world: int, dev):
   """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides,
-  maximum over ranks (the driver's contract); returns seconds."""
+  maximum over ranks (the driver's contract); returns (seconds, what the last step returned)."""
   for _ in range(warmup):
     fn()
   torch.cuda.synchronize()
@@ -496,7 +545,7 @@ def timed_region(fn, steps: int, warmup: int, world: int, dev):
   torch.cuda.synchronize()
   t0 = time.perf_counter()
   for _ in range(steps):
-    fn()
+    out = fn()
   torch.cuda.synchronize()
   if world > 1:
     dist.barrier()
@@ -504,7 +553,7 @@ def timed_region(fn, steps: int, warmup: int, world: int, dev):
   t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
   if world > 1:
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
-  return float(t.item())
+  return float(t.item()), out
 
 
 def run_streaming128(args, rank: int, world: int, dev, rccl_ranks: int):
@@ -544,10 +593,13 @@ def run_streaming128(args, rank: int, world: int, dev, rccl_ranks: int):
 
   rows = shard_rows(lo, hi)
   layer = ftk.ShardedStreaming(k=TOPK).index_from_dataset(dataset(rows), base_row=lo)
-  elapsed = timed_region(lambda: layer(queries), args.steps, args.warmup, world, dev)
+  elapsed, out = timed_region(lambda: layer(queries), args.steps, args.warmup, world, dev)
   value = BATCH / (elapsed / args.steps)
   if rank != 0:
     return None
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, {"scores": out[0], "rows": out[1]})
+  del out
   flop = 2.0 * BATCH * (hi - lo) * d
   ms = elapsed / args.steps * 1e3
   result = {"metric": "queries/sec streaming top-100", "value": value, "unit": "queries/s", "n_gpus": world,
@@ -567,7 +619,7 @@ def run_streaming128(args, rank: int, world: int, dev, rccl_ranks: int):
                          "frac": flop / (ms * 1e-3) / 1e12 / F16_MFMA_PEAK_TFLOPS, "traffic": None,
                          "algorithmic_flop_per_step": flop, "note": "per-GPU flop over the whole call"},
             "exchange_bytes_per_rank": 2 * BATCH * TOPK * 4}
-  if world > 1 and not args.no_single_gpu_reference:
+  if args.full and world > 1 and not args.no_single_gpu_reference:
     del layer, rows
     torch.cuda.empty_cache()
     allrows = shard_rows(0, total)
@@ -620,10 +672,17 @@ def run_dlrm_embedding(args, rank: int, world: int, dev, rccl_ranks: int):
     layer.stage(batches[state["i"] % len(batches)])      # the next batch's split sizes, one step ahead
     out.backward(upstream)
     opt.step()
+    # (held past the step only for --dump-outputs: a [batch, 100, 32] lookup is 1.7 GB at the full batch)
+    return out.detach() if args.dump_outputs else None
 
-  elapsed = timed_region(step, args.steps, args.warmup, world, dev)
+  elapsed, out = timed_region(step, args.steps, args.warmup, world, dev)
   if rank != 0:
     return None
+  if args.dump_outputs:
+    # the last step's looked-up rows and the shard's table rows after its update: seeded samples of 65536 rows each
+    dump_outputs(args.dump_outputs, {"lookup_rows": sample_rows(out.reshape(-1, d), 65536, 1),
+                                     "table_rows": sample_rows(layer.embeddings.detach(), 65536, 2)})
+  del out
   ms = elapsed / args.steps * 1e3
   remote = (world - 1) / world
   # gather n * (D*4 read + D*4 write) + ids; scatter/Adagrad nnz*D*4 + 4*uniq*D*4 (uniq ~ nnz here)
@@ -846,6 +905,8 @@ def main() -> None:
   value = BATCH / (elapsed / steps)
   local = index._local if world > 1 else index
   redo = local.last_redo_count()
+  if rank == 0 and args.dump_outputs:
+    dump_outputs(args.dump_outputs, {"scores": out[0], "indices": out[1]})
 
   if rank == 0:
     dom = max(kinds, key=lambda kk: kinds[kk][0])          # the kernel the step spends most time in
@@ -904,17 +965,18 @@ def main() -> None:
                          "the clock follows the power the operand data draws (profiles/r05_mfma_peak.txt)",
         },
     }
-    # this box's own ceilings, measured after the timed region (csrc/calibrate.hip through bench_legs.measure_ceilings)
-    import bench_legs
-    ceilings = bench_legs.measure_ceilings(dev)
-    roof = result["roofline"]
-    roof["shader_mhz"] = ceilings["shader_mhz"]
-    roof["measured_copy_gbs"] = ceilings["copy_gbs"]
-    if dom >= 1:
-      roof["measured_ceiling"] = ceilings["mfma_f16_tflops"]
-      roof["frac_of_measured_ceiling"] = achieved / ceilings["mfma_f16_tflops"]
-    roof["measured_ceiling_note"] = ceilings["note"]
-    if world == 1 and workload == "headline":
+    if args.full:
+      # this box's own ceilings, measured after the timed region (csrc/calibrate.hip through bench_legs.measure_ceilings)
+      import bench_legs
+      ceilings = bench_legs.measure_ceilings(dev)
+      roof = result["roofline"]
+      roof["shader_mhz"] = ceilings["shader_mhz"]
+      roof["measured_copy_gbs"] = ceilings["copy_gbs"]
+      if dom >= 1:
+        roof["measured_ceiling"] = ceilings["mfma_f16_tflops"]
+        roof["frac_of_measured_ceiling"] = achieved / ceilings["mfma_f16_tflops"]
+      roof["measured_ceiling_note"] = ceilings["note"]
+    if args.full and world == 1 and workload == "headline":
       cpu_inputs = None
       if not args.no_cpu_baseline:   # (inputs of the CPU leg, which runs after every GPU measurement;
         cpu_inputs = (index.candidates(), out[1][:64].clone())   # still on the device here)
@@ -995,7 +1057,7 @@ def main() -> None:
             "note": "a prediction from single-GPU measurements, not a scaling measurement: assumes all eight shards "
                     "take the time rank 0's shard takes here and ignores clock / power interactions between GPUs"}
         del shard, gathered
-    if world == 1 and workload == "headline" and not args.no_cpu_baseline:
+    if args.full and world == 1 and workload == "headline" and not args.no_cpu_baseline:
       # the CPU legs come LAST: their host threads would disturb the GPU measurements above
       from oracle import cpu_path  # checker-side code: only this baseline leg uses it
       corpus_host, q_host, gpu_idx64 = cpu_inputs[0].cpu().numpy(), queries.cpu().numpy(), cpu_inputs[1].cpu().numpy()
@@ -1017,7 +1079,7 @@ def main() -> None:
       if "config_legs" in result:
         import bench_legs
         bench_legs.add_cpu_baselines(result["config_legs"])
-    if world > 1 and not args.no_single_gpu_reference:
+    if args.full and world > 1 and not args.no_single_gpu_reference:
       # the SAME workload on one GPU, measured by rank 0 after the timed region (the other ranks
       # wait at the final barrier): makes the N > 1 line self-contained -- speedup = value / this --
       # because the N = 1 bench line is the 1M x 64 headline, not this corpus

@@ -82,3 +82,21 @@ def test_compact_handles_a_minimal_result_and_non_finite_numbers():
                                            "frac": 1.25e-4, "traffic": None}})
   obj = json.loads(line)        # strict JSON: NaN became null
   assert obj["value"] is None and obj["legs"] == {}
+
+
+def _bench(*argv):
+  import subprocess
+  import sys
+  return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(argv), capture_output=True, text=True,
+                        timeout=120)
+
+
+def test_bench_options_plain_run_full_and_dump():
+  """A plain run times the headline only; `--full` adds every other leg; `--dump-outputs DIR` writes the last
+  timed step's outputs.  (Argument parsing happens before torch is imported: no GPU needed.)"""
+  r = _bench("--help")
+  assert r.returncode == 0, r.stderr
+  for opt in ("--full", "--dump-outputs", "--steps", "--warmup", "--gpus"):
+    assert opt in r.stdout, opt
+  r = _bench("--steps", "0")
+  assert r.returncode != 0 and "--steps" in r.stderr
