@@ -637,6 +637,39 @@ int tfrs_dot_interaction_bwd_strided(const float *x, const float *dout, int64_t 
  * concat path, so a forward can never succeed where its backward would return TFRS_ENOTIMPL. */
 int tfrs_dot_interaction_strided_supported(int64_t batch, int f, int d, int self_interaction);
 
+/* ------------------------------------------------------------------------- *
+ * ScaNN search (layers/factorized_top_k.py:613-796; csrc/scann.hip): partitioned, product-quantized approximate
+ * top-K for ONE chunk of nq queries.  The caller has run the leaf pass (exact top-l_eff of q . mu over the leaf
+ * centres: probes[nq, l_eff] leaf numbers, leaf_scores[nq, l_eff] their f32 fma-chain scores) and holds the index:
+ *   leaf_offsets[num_leaves + 1] (int64): leaf l is positions leaf_offsets[l] .. leaf_offsets[l + 1] of the
+ *     leaf-major order, perm[position] (int32) is the original row; max_leaf_rows = largest leaf (host value);
+ *   codes[(n + 128) * code_bytes]: 4-bit code of block b (dims b * dims_per_block ..) in the low (b even) / high
+ *     (b odd) nibble of byte b / 2 of the position's code row; the last 128 rows are padding (read, never used);
+ *     code_bytes is a multiple of 4, at most 64;
+ *   lut: fp16 [dp][16], dp = d rounded up to 16: codebook value of dimension i under code c, times 2^lut_exp
+ *     (zero for i >= d);
+ *   rows[n, d] (f32, leaf-major) or NULL: with rows the top-r candidates are re-scored exactly.
+ * p_max >= every query's probed rows P_b = sum of its l_eff leaf sizes; the workspace holds an [nq, p_max] score
+ * buffer.  Results out_scores / out_rows [nq, k], (score desc, original row asc): with rows, the scores are the
+ * d-ordered f32 fma chain (== BruteForce, oracle/topk.py scores) of the best k of the top min(r, p_max)
+ * approximate candidates; without, the approximate scores s~ of the top k.
+ *
+ * Approximate score of row x of leaf l (decoded residual r^ = the codebook values of its codes):
+ *   s~ = (sum_i fp16(q_i 2^eq) fp16(r^_i 2^lut_exp), f32 MFMA accumulation) * 2^-(eq + lut_exp) + (q . mu_l)_f32,
+ * where 2^eq puts max|q| into [2^13, 2^14) and 2^lut_exp does the same for the largest codebook value |C|max
+ * (the caller's choice), so no finite input overflows fp16 and what flushes is below 2^-38 of the maximum.  Against
+ * the float64 value s = sum_i q_i (mu_i + r^_i) of the same decoded vector:
+ *   |s~ - s| <= 2^-9 * sum_i |q_i| (|mu_i| + |r^_i|) + 2^-32 * d * max|q| * |C|max
+ * (2^-10 + 2^-22 for the two fp16 roundings, (d + 10) 2^-24 for the f32 sums, d 2^-37 max|q| |C|max for flushes).
+ * Rows are distinct within a query; columns past P_b never appear ahead of probed rows.
+ * ------------------------------------------------------------------------- */
+size_t tfrs_scann_search_workspace_bytes(int64_t nq, int num_leaves, int l_eff, int d, int64_t p_max, int r);
+int tfrs_scann_search(const float *queries, int64_t nq, int d, const int32_t *probes, const float *leaf_scores,
+                      int l_eff, const int64_t *leaf_offsets, int num_leaves, int64_t max_leaf_rows,
+                      const uint8_t *codes, int code_bytes, const void *lut, int dims_per_block, int lut_exp,
+                      const int32_t *perm, const float *rows, int64_t p_max, int r, int k, float *out_scores,
+                      int32_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ SOURCES = [
     "logits_ce.hip",
     "interaction.hip",
     "gemm16.hip",
+    "scann.hip",
 ]
 
 
