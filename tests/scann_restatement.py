@@ -1,4 +1,4 @@
-"""Float64 NumPy restatement of the ScaNN search (recommenders_amd/layers/factorized_top_k.py ``ScaNN``), working from
+"""Float64 NumPy restatement of the ScaNN search (recommenders_amd/layers/factorized_top_k/scann.py ``ScaNN``), working from
 a layer's ``state_dict``: probe sets with ``L_eff``, the approximate score s~ of the decoded vectors with the error
 bound of include/tfrs_hip.h, and the band-aware checks of a returned top-k.  Test infrastructure only."""
 

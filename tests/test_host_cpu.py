@@ -278,7 +278,7 @@ assert np.array_equal(s.numpy(), es)
 big = 5_000_000_000
 base = big + (n - hi)                     # rank 0 -> the LAST rows of the corpus
 wide = ftk.ShardedBruteForce(k=k, local_search=local_search, merge=merge).index(cand[lo:hi], base_row=base)
-assert wide._wide
+assert wide._rows64
 s2, i2 = wide(qry)
 assert i2.dtype == torch.int64
 # the same corpus in global-row order: rank 1's rows first
@@ -591,7 +591,7 @@ assert np.array_equal(i.numpy(), ei) and np.array_equal(s.numpy(), es)
 # ShardedBruteForce: global rows beyond int32 switch every rank to the int64 exchange (round 4; refused
 # before); a negative base row is still an error
 wide = ftk.ShardedBruteForce(k=5, local_search=lambda *a: None).index(cand[:10], base_row=2**31 - 5)
-assert wide._wide
+assert wide._rows64
 try:
   ftk.ShardedBruteForce(k=5, local_search=lambda *a: None).index(cand[:10], base_row=-1)
   raise SystemExit("expected ValueError")

@@ -338,8 +338,21 @@ def test_chunking(reorder, monkeypatch):
   layer = ftk.ScaNN(k=10, num_leaves=200, num_leaves_to_search=20, num_reordering_candidates=reorder).index(c)
   s1, i1 = layer(q)
   _, p_max = layer.probe_plan()
-  monkeypatch.setattr(ftk, "_SCANN_SCORE_BUDGET_BYTES", 4 * p_max * 100)   # 100 queries per chunk: 3 chunks
+  from recommenders_amd import _lib
+  from recommenders_amd.layers.factorized_top_k import scann as scann_module   # (the module that reads the budget)
+  lib, search, sizes = _lib.load(), _lib.load().tfrs_scann_search, []
+
+  def counted_search(queries, nq, *rest):
+    sizes.append(nq)
+    return search(queries, nq, *rest)
+
+  monkeypatch.setattr(lib, "tfrs_scann_search", counted_search)
+  layer(q)
+  assert sizes == [300]                                                    # the default budget: one chunk
+  del sizes[:]
+  monkeypatch.setattr(scann_module, "_SCANN_SCORE_BUDGET_BYTES", 4 * p_max * 100)   # 100 queries per chunk: 3 chunks
   s2, i2 = layer(q)
+  assert sizes == [100, 100, 100]
   np.testing.assert_array_equal(_np(i1), _np(i2))
   np.testing.assert_array_equal(_np(s1), _np(s2))
 

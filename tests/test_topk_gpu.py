@@ -979,3 +979,75 @@ def test_streaming_reports_nonfinite_queries():
   with pytest.raises(ValueError, match="NaN or Inf"):
     layer(q)
   np.testing.assert_array_equal(_np(layer(q)[1]), want)
+
+
+def _reindex_steps():
+  """(name, constructor arguments, index function, corpus) of the ways to index a ``BruteForce``."""
+  rng = np.random.default_rng(41)
+  wide = rng.normal(size=(700, 160)).astype(np.float32)
+  narrow = rng.normal(size=(900, 64)).astype(np.float32)
+  dup = narrow[rng.integers(0, 40, size=600)]                  # 40 distinct rows
+
+  def streamed(layer, c):
+    return layer.index_from_dataset([c[lo:lo + 250] for lo in range(0, len(c), 250)], total_rows=len(c))
+
+  return {"wide": ({}, lambda layer, c: layer.index(c), wide),
+          "streamed": ({}, streamed, narrow),
+          "dedup": ({"dedup": True}, lambda layer, c: layer.index(c), dup)}
+
+
+@pytest.mark.parametrize("first,second", [("wide", "streamed"), ("streamed", "wide"), ("dedup", "wide")])
+def test_reindex_replaces_the_whole_index_state(first, second, filter_mode):
+  """Every way of indexing drops ALL of the previous index: a layer that held a wide (d > 128) corpus and is
+  re-indexed through the streamed ingest with d <= 128 (and the other way round, and a de-duplicated corpus
+  followed by a wide one) answers bit for bit like a freshly constructed layer, holds the new corpus, and
+  reports no redo before its first call.  (While the index state was a set of separate attributes, the streamed
+  ingest left the wide copy in place: wide -> streamed kept serving, and ``candidates()`` kept returning, the
+  previous corpus.)"""
+  ftk = _layers()
+  steps = _reindex_steps()
+  kwargs, index_first, corpus_first = steps[first]
+  _, index_second, corpus = steps[second]
+  k = 20
+  layer = index_first(ftk.BruteForce(k=k, **kwargs), corpus_first)
+  layer(np.random.default_rng(42).normal(size=(5, corpus_first.shape[1])).astype(np.float32))
+  if first == "dedup":
+    assert layer._dup is not None
+  assert index_second(layer, corpus) is layer
+  assert layer.last_redo_count() == 0
+  fresh = index_second(ftk.BruteForce(k=k, **kwargs), corpus)
+  np.testing.assert_array_equal(_np(layer.candidates()), corpus)
+  q = np.random.default_rng(43).normal(size=(33, corpus.shape[1])).astype(np.float32)
+  s, i = layer(q)
+  fs, fi = fresh(q)
+  np.testing.assert_array_equal(_np(s), _np(fs))
+  np.testing.assert_array_equal(_np(i), _np(fi))
+  if corpus.shape[1] <= ftk.MAX_FUSED_DIM:       # (the fused scan is exact; the wide path's scores are GEMM sums)
+    es, ei = o_topk.brute_force(q, corpus, k)
+    np.testing.assert_array_equal(_np(s), es)
+    np.testing.assert_array_equal(_np(i), ei)
+
+
+@pytest.mark.parametrize("name", ["bruteforce", "scann", "scann_noreorder"])
+def test_saved_indexes_load_across_versions(name, tmp_path, filter_mode):
+  """The ``.npz`` files under tests/golden/ were written by ``BruteForce.save`` / ``ScaNN.save`` while this
+  package was a single module (tests/golden/make_saved_indexes.py): they load, answer the stored queries with the
+  stored (scores, identifiers) bit for bit, and saving again writes the same keys, dtypes and arrays."""
+  import os
+  from tests.conftest import GOLDEN
+  ftk = _layers()
+  cls = ftk.BruteForce if name == "bruteforce" else ftk.ScaNN
+  stored = os.path.join(GOLDEN, f"saved_{name}.npz")
+  layer = cls.load(stored)
+  with np.load(os.path.join(GOLDEN, "saved_expected.npz"), allow_pickle=False) as f:
+    q, want_s, want_i = f["queries"], f[f"{name}_scores"], f[f"{name}_identifiers"]
+  s, i = layer(q)
+  np.testing.assert_array_equal(_np(s), want_s)
+  np.testing.assert_array_equal(np.asarray(_np(i)), want_i)
+  again = str(tmp_path / "again.npz")
+  layer.save(again)
+  with np.load(stored, allow_pickle=False) as old, np.load(again, allow_pickle=False) as new:
+    assert sorted(new.files) == sorted(old.files)
+    for key in old.files:
+      assert new[key].dtype == old[key].dtype and new[key].shape == old[key].shape, key
+      np.testing.assert_array_equal(new[key], old[key], err_msg=key)
