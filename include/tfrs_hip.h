@@ -662,6 +662,7 @@ int tfrs_dot_interaction_strided_supported(int64_t batch, int f, int d, int self
  *   |s~ - s| <= 2^-9 * sum_i |q_i| (|mu_i| + |r^_i|) + 2^-32 * d * max|q| * |C|max
  * (2^-10 + 2^-22 for the two fp16 roundings, (d + 10) 2^-24 for the f32 sums, d 2^-37 max|q| |C|max for flushes).
  * Rows are distinct within a query; columns past P_b never appear ahead of probed rows.
+ * tfrs_scann_search_workspace_bytes is 0 when any argument is below 1 (a call with nq = 0 needs no workspace).
  * ------------------------------------------------------------------------- */
 size_t tfrs_scann_search_workspace_bytes(int64_t nq, int num_leaves, int l_eff, int d, int64_t p_max, int r);
 int tfrs_scann_search(const float *queries, int64_t nq, int d, const int32_t *probes, const float *leaf_scores,

@@ -330,7 +330,7 @@ using namespace tfrs;
 
 extern "C" size_t tfrs_scann_search_workspace_bytes(int64_t nq, int num_leaves, int l_eff, int d, int64_t p_max,
                                                     int r) {
-  if (nq < 0 || num_leaves < 1 || l_eff < 1 || d < 1 || p_max < 1 || r < 1) return 0;
+  if (nq < 1 || num_leaves < 1 || l_eff < 1 || d < 1 || p_max < 1 || r < 1) return 0;
   const int dp = (d + 15) / 16 * 16;
   return scann_layout(nullptr, nq, num_leaves, l_eff, dp, p_max, (int)std::min<int64_t>(r, p_max)).total;
 }

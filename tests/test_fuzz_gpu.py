@@ -17,7 +17,8 @@ def _load(name):
 
 
 @pytest.mark.parametrize("name,seed,cases", [("fuzz_topk", 11, 5), ("fuzz_streaming", 12, 3),
-                                             ("fuzz_gemm", 13, 5), ("fuzz_embedding", 14, 5)])
+                                             ("fuzz_gemm", 13, 5), ("fuzz_embedding", 14, 5),
+                                             ("fuzz_scann", 15, 6)])
 def test_fuzzers_find_nothing(name, seed, cases, monkeypatch):
   for key in ("TFRS_TOPK_FILTER", "TFRS_TOPK_STAT", "TFRS_GEMM_MODE"):
     monkeypatch.delenv(key, raising=False)

@@ -1,5 +1,6 @@
-"""factorized_top_k.ScaNN without a GPU: import, constructor validation, the host probe planner (property-tested) and
-the cross-compiled scan kernels (MFMA wait states, no scratch)."""
+"""factorized_top_k.ScaNN without a GPU: import, constructor validation, the host probe planner (property-tested), the
+argument checks of tfrs_scann_search and its workspace size, and the cross-compiled scan kernels (MFMA wait states, no
+scratch)."""
 
 import os
 import re
@@ -81,6 +82,63 @@ def test_probe_plan_examples():
   assert plan([10] * 100, 10, 10) == (10, 100)
   assert plan([5, 1, 1, 100], 2, 3) == (3, 106)
   assert plan([5, 1, 1, 100], 9, 3) == (4, 107)
+
+
+@pytest.fixture(scope="module")
+def lib():
+  import __graft_entry__
+  __graft_entry__.build()
+  from recommenders_amd import _lib
+  return _lib.load()
+
+
+_SEARCH_DEFAULTS = dict(nq=0, d=20, l_eff=3, num_leaves=8, max_leaf_rows=100, code_bytes=8, dims_per_block=2,
+                        lut_exp=0, p_max=300, r=20, k=10)
+
+
+def _search(lib, **over):
+  """tfrs_scann_search with NULL pointers and one or more arguments changed: validation only, nothing is launched."""
+  a = dict(_SEARCH_DEFAULTS, **over)
+  return lib.tfrs_scann_search(None, a["nq"], a["d"], None, None, a["l_eff"], None, a["num_leaves"],
+                               a["max_leaf_rows"], None, a["code_bytes"], None, a["dims_per_block"], a["lut_exp"],
+                               None, None, a["p_max"], a["r"], a["k"], None, None, None, 0, None)
+
+
+@pytest.mark.parametrize("over,names", [
+    (dict(code_bytes=6), "code_bytes=6"),                                    # not a multiple of 4
+    (dict(code_bytes=68), "code_bytes=68"),                                  # above the 64-byte ceiling
+    (dict(d=128, dims_per_block=1, code_bytes=60), "code_bytes=60"),         # 128 blocks need 64 bytes
+    (dict(r=5), "r=5"),                                                      # r < k
+    (dict(r=1025), "r=1025"),
+    (dict(p_max=5), "p_max=5"),                                              # p_max < k
+    (dict(l_eff=9), "l_eff=9"),                                              # above num_leaves = 8
+    (dict(dims_per_block=21), "dims_per_block=21"),                          # above d = 20
+    (dict(d=129, dims_per_block=2), "dim=129"),
+    (dict(nq=1 << 20, l_eff=4096, num_leaves=4096), "nq * l_eff"),           # 2^32 (query, probe) pairs
+])
+def test_search_validates_before_it_touches_the_device(lib, over, names):
+  """Every argument check of tfrs_scann_search comes before its nq == 0 return and before any HIP call: with nq = 0
+  (or NULL pointers) a bad argument is TFRS_EINVAL and tfrs_last_error names it; the same call with good arguments
+  is TFRS_OK."""
+  from recommenders_amd import _lib
+  assert _search(lib) == _lib.TFRS_OK
+  assert _search(lib, **over) == _lib.TFRS_EINVAL
+  assert "scann_search" in _lib.last_error() and names in _lib.last_error(), _lib.last_error()
+
+
+def test_search_workspace_bytes(lib):
+  """0 for a non-positive argument, growing with every argument, and capped in r at p_max (the selection never holds
+  more than the score row)."""
+  ws = lib.tfrs_scann_search_workspace_bytes
+  base = dict(nq=64, num_leaves=100, l_eff=10, d=20, p_max=5000, r=100)
+  order = ("nq", "num_leaves", "l_eff", "d", "p_max", "r")
+  size = lambda **over: int(ws(*[dict(base, **over)[name] for name in order]))
+  assert size() > 4 * 64 * 5000
+  for name in order:
+    assert size(**{name: 0}) == 0, name
+    assert size(**{name: -1}) == 0, name
+    assert size(**{name: 2 * base[name]}) > size(), name
+  assert size(r=5000) == size(r=5001) == size(r=1 << 20)
 
 
 _ASM = {}
