@@ -127,6 +127,9 @@ __host__ __device__ inline int64_t padded_rows(int64_t n) {
 //                  <= ||q|| * N * (2^-10 + 2^-23 sqrt(D)),  N = max row norm of the stage
 //   + D * 2^-21 ||q|| ||c|| for the f32 accumulation orders (matrix core vs. fma chain)
 // so kappa = 2^-10 + 2^-19.5 + 2^-14 (D = 128) = 1.04e-3; kF16Kappa adds 5 %.
+// The last term is stated for ANY order in which D products are accumulated in f32, so it covers both MFMA shapes of
+// topk_scan16.hip (32x32x16: D / 16 links of 16 products, 16x16x32: D / 32 links of 32); measured per shape in
+// tests/test_scan16_mfma_shape_gpu.py.
 // Row r of the image occupies row_bytes16(dp16) bytes: dp16 halves in natural feature order
 // + one 16-byte zero pad slot (odd number of 16-B slots per row -> conflict-free
 // ds_read_b128, same argument as the f32 image).  Per stage: StageMeta {norm, scale}.
