@@ -396,6 +396,26 @@ int tfrs_embedding_scatter_add_rowscan_multi(int ntables, const float *const *gr
  * or sqrt(acc) + eps (mode 2), the same arithmetic as the fused sparse update above.  Host arrays of device pointers. */
 int tfrs_adagrad_dense_multi(int ntensors, float *const *params_h, float *const *accum_h, const float *const *grads_h,
                              const int64_t *n_h, float lr, float eps, int mode, void *stream);
+/* ClippyAdagrad (experimental/optimizers/clippy_adagrad.py:188-254 with shrink_by_references, :21-70) on up to 32 dense
+ * tensors per call, f32:
+ *   [mode 2: acc += g * g first]   pre = 1 / sqrt(acc + eps);   delta = lr * g * pre;
+ *   maxd = |w| * var_rel + pre * acc_rel + abs_thr;   factor = min(1, min_i (delta_i == 0 ? 1 : maxd_i / |delta_i|));
+ *   w -= delta * factor;   [mode 0: acc += g * g after;  mode 1 (clip_accumulator_update): acc += (g * factor)^2 after]
+ * Host arrays of device pointers as in tfrs_adagrad_dense_multi; factors[ntensors] is a DEVICE array that receives each
+ * tensor's factor (re-armed to 1 by the call itself; it never visits the host: no synchronisation, capturable).  A factor
+ * pass (reads only, atomicMin on the float's bits) and an apply pass over the same elements. */
+int tfrs_clippy_dense_multi(int ntensors, float *const *params_h, float *const *accum_h, const float *const *grads_h,
+                            const int64_t *n_h, float *factors, float lr, float eps, float var_rel, float acc_rel,
+                            float abs_thr, int mode, void *stream);
+/* The same on the looked-up rows of table[vocab, d] from UNSORTED ids (int32 / int64) and grad_out[n, d]: duplicates
+ * are summed first, strictly in occurrence order; ids outside [0, vocab) are ignored; the factor (*factor, device) is
+ * the min over the touched rows only; untouched rows of table and accum are not written.  rowscan != 0: the sort-free
+ * row scan (d <= 256, small vocab * n), else radix sort + segments with workspace from
+ * tfrs_clippy_sparse_workspace_bytes(n, rowscan).  n == 0: factor 1, nothing written. */
+size_t tfrs_clippy_sparse_workspace_bytes(int64_t n, int rowscan);
+int tfrs_clippy_sparse(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d, int64_t vocab,
+                       float *table, float *accum, float *factor, float lr, float eps, float var_rel, float acc_rel,
+                       float abs_thr, int mode, int rowscan, void *workspace, size_t workspace_bytes, void *stream);
 /* Up to 16 device buffers copied in ONE launch: a batch's input tensors into the static buffers of a captured
  * train / test step (the `Model.fit` loop of models/base.py:64-85 replays HIP graphs; README.md:84-98).  Host arrays of
  * device pointers and byte counts; buffers must not overlap. */

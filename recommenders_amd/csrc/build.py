@@ -32,6 +32,7 @@ SOURCES = [
     "metric_fused.hip",
     "dedup.hip",
     "embedding.hip",
+    "clippy.hip",
     "shard_route.hip",
     "hashing.hip",
     "softmax.hip",

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "clippy.h"
 
 namespace tfrs {
 
@@ -323,11 +324,14 @@ constexpr int kRowscanHitCap = 128;
 // NS = number of 64-feature groups of a row (d <= 64 * NS): a template parameter so that every load of the gradient-row
 // fetch is unconditional -- a load under `if (lane + 64 s < d)` makes the number of loads in flight unknown to the
 // compiler, which then waits for each one (the ISA of the runtime-d version: 176 loads, at most ONE in flight).
-template <typename IdT, int NS>
+// CLIPPY: 0 = the scatter-add / Adagrad epilogue; 1 / 2 = the factor / apply pass of ClippyAdagrad on the touched rows
+// (clippy_rowscan_kernel below: the same scan and the same occurrence-order sums, another epilogue).
+template <typename IdT, int NS, int CLIPPY = 0>
 __device__ __forceinline__ void scatter_rowscan_body_ns(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d,
     int64_t vocab, float *__restrict__ dst, float *__restrict__ accum, float lr, float eps,
-    int adagrad, int64_t block, int32_t *s_ids, int *s_hits) {
+    int adagrad, int64_t block, int32_t *s_ids, int *s_hits, float *__restrict__ factor_slot = nullptr,
+    const ClippyHyper *clippy = nullptr) {
   // the id list goes through LDS in chunks shared by the workgroup's 4 rows, so a wave's scan
   // is 64 LDS reads per 4096 ids instead of 64 dependent global loads
   constexpr int kChunk = kRowscanChunk;
@@ -405,6 +409,36 @@ __device__ __forceinline__ void scatter_rowscan_body_ns(
       __builtin_amdgcn_wave_barrier();
     }
     flush();
+  }
+  if (CLIPPY) {
+    const float factor = CLIPPY == 2 ? *factor_slot : 1.0f;
+    float m = 1.0f;
+    if (row_ok && touched) {   // wave-uniform
+      float av[NS], pv[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        av[s] = accum[v * d + fo[s]];
+        pv[s] = dst[v * d + fo[s]];
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (fok[s]) {
+          const ClippyElement e = clippy_element(pv[s], av[s], g[s], *clippy);
+          if (CLIPPY == 2) {
+            clippy_apply(e, g[s], factor, *clippy, pv[s], av[s]);
+            accum[v * d + fo[s]] = av[s];
+            dst[v * d + fo[s]] = pv[s];
+          } else {
+            m = clippy_min_scale(m, e);
+          }
+        }
+      }
+    }
+    if (CLIPPY == 1) {
+      m = clippy_wave_min(m);
+      if (lane == 0) clippy_factor_min(factor_slot, m);
+    }
+    return;
   }
   if (!row_ok) return;
   if (adagrad) {
@@ -929,30 +963,16 @@ extern "C" size_t tfrs_embedding_scatter_add_workspace_bytes(int64_t n) {
          tfrs::sort_al((tiles * 4 / tfrs::kScanChunk + 1) * 1024 * 4);
 }
 
-// Backward of gather from UNSORTED ids: own radix sort + the segmented scatter-add / fused
-// Adagrad above.  ids outside [0, vocab) are ignored (they read as zero rows in the forward).
-extern "C" int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const void *ids,
-                                                   int ids_are_i64, int64_t n, int d, int64_t vocab,
-                                                   float *grad_table_or_table, float *accum, float lr,
-                                                   float eps, int adagrad, void *workspace,
-                                                   size_t workspace_bytes, void *stream) {
-  using namespace tfrs;
-  TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "embedding_scatter_add_unsorted: bad shape");
-  TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll,
-                 "embedding_scatter_add_unsorted: vocab / n must fit 32 bits");
-  if (n == 0) return TFRS_OK;
-  TFRS_CHECK_ARG(grad_out && ids && grad_table_or_table && workspace,
-                 "embedding_scatter_add_unsorted: NULL pointer");
-  TFRS_CHECK_ARG(!adagrad || accum, "embedding_scatter_add_unsorted: Adagrad needs an accumulator");
-  if (workspace_bytes < tfrs_embedding_scatter_add_workspace_bytes(n)) {
-    set_error("embedding_scatter_add_unsorted: workspace too small");
-    return TFRS_ENOMEM;
-  }
-  hipStream_t s = (hipStream_t)stream;
+// The sort alone: (id, position) pairs of `ids` in `workspace` (tfrs_embedding_scatter_add_workspace_bytes(n)), stable,
+// ids outside [0, vocab) last.  Returns the index `cur` of the sorted buffers: sorted ids = keys[cur], positions =
+// vals[cur]; keys[cur ^ 1] (n uint32) is free.  Shared by the scatter-add / Adagrad update and ClippyAdagrad's two passes.
+namespace tfrs {
+static int sort_id_positions(const void *ids, int ids_are_i64, int64_t n, int64_t vocab, void *workspace, hipStream_t s,
+                             uint32_t *(&keys)[2], uint32_t *(&vals)[2]) {
   char *w = static_cast<char *>(workspace);
   const size_t kb = sort_al((size_t)n * 4);
-  uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(w), reinterpret_cast<uint32_t *>(w + kb)};
-  uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(w + 2 * kb), reinterpret_cast<uint32_t *>(w + 3 * kb)};
+  keys[0] = reinterpret_cast<uint32_t *>(w); keys[1] = reinterpret_cast<uint32_t *>(w + kb);
+  vals[0] = reinterpret_cast<uint32_t *>(w + 2 * kb); vals[1] = reinterpret_cast<uint32_t *>(w + 3 * kb);
   const int64_t tiles = (n + kSortTile - 1) / kSortTile;
   uint32_t *hist = reinterpret_cast<uint32_t *>(w + 4 * kb);
   uint32_t *offs = reinterpret_cast<uint32_t *>(w + 4 * kb + sort_al((size_t)tiles * 4096 * 4));
@@ -989,6 +1009,32 @@ extern "C" int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const 
     else if (digit_bits == 9) one_pass(std::integral_constant<int, 9>{}, p);
     else one_pass(std::integral_constant<int, 8>{}, p);
   }
+  return cur;
+}
+}  // namespace tfrs
+
+// Backward of gather from UNSORTED ids: own radix sort + the segmented scatter-add / fused
+// Adagrad above.  ids outside [0, vocab) are ignored (they read as zero rows in the forward).
+extern "C" int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const void *ids,
+                                                   int ids_are_i64, int64_t n, int d, int64_t vocab,
+                                                   float *grad_table_or_table, float *accum, float lr,
+                                                   float eps, int adagrad, void *workspace,
+                                                   size_t workspace_bytes, void *stream) {
+  using namespace tfrs;
+  TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "embedding_scatter_add_unsorted: bad shape");
+  TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll,
+                 "embedding_scatter_add_unsorted: vocab / n must fit 32 bits");
+  if (n == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(grad_out && ids && grad_table_or_table && workspace,
+                 "embedding_scatter_add_unsorted: NULL pointer");
+  TFRS_CHECK_ARG(!adagrad || accum, "embedding_scatter_add_unsorted: Adagrad needs an accumulator");
+  if (workspace_bytes < tfrs_embedding_scatter_add_workspace_bytes(n)) {
+    set_error("embedding_scatter_add_unsorted: workspace too small");
+    return TFRS_ENOMEM;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t *keys[2], *vals[2];
+  const int cur = sort_id_positions(ids, ids_are_i64, n, vocab, workspace, s, keys, vals);
   TFRS_LAUNCH_CHECK();
   const bool vec = (d % 4 == 0) && (((uintptr_t)grad_out) % 16 == 0) &&
                    (((uintptr_t)grad_table_or_table) % 16 == 0) && (!accum || ((uintptr_t)accum) % 16 == 0);
@@ -1212,6 +1258,173 @@ extern "C" int tfrs_embedding_scatter_add_rowscan(const float *grad_out, const v
     hipLaunchKernelGGL((scatter_rowscan_kernel<int64_t>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr, eps, adagrad);
   else
     hipLaunchKernelGGL((scatter_rowscan_kernel<int32_t>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr, eps, adagrad);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+// ---- ClippyAdagrad on the looked-up rows of a table (experimental/optimizers/clippy_adagrad.py:188-254 on IndexedSlices) ----
+// The factor is the min over the TOUCHED rows (the reference gathers variable and accumulator at the indices), after
+// duplicates are summed.  Two passes (clippy.h) over the same id structure: the row scan for small tables (scatter_rowscan_body_ns with its
+// ClippyAdagrad epilogue), or ONE sort
+// and two segmented passes.  The summed rows are RECOMPUTED in the apply pass, not kept: the same loads added in the
+// same order give the same bits, it needs no [n, d] workspace (870 MB at 1.7 M x 128), and re-reading the gradient rows
+// (n d 4 bytes) costs no more than writing and re-reading their sums would.  A run of equal ids is summed by one
+// thread strictly in occurrence order -- not cut into parallel pieces like scatter_add_u32_kernel's: the factor's
+// error bound is stated against the sequential f32 sum.
+namespace tfrs {
+
+template <int VEC, bool APPLY>
+__global__ void __launch_bounds__(256) clippy_sorted_kernel(
+    const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids, const uint32_t *__restrict__ perm,
+    int64_t n, int d, uint32_t vocab, float *__restrict__ table, float *__restrict__ accum,
+    float *__restrict__ factor_slot, const ClippyHyper h) {
+  const int per_row = d / VEC;
+  const int64_t total = n * per_row;
+  const float factor = APPLY ? *factor_slot : 1.0f;
+  float m = 1.0f;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / per_row;
+    const int c = (int)(t - i * per_row);
+    const uint32_t id = sorted_ids[i];
+    const uint32_t id_prev = sorted_ids[i > 0 ? i - 1 : 0];
+    if (id >= vocab) continue;                       // invalid / padding id
+    if (i > 0 && id_prev == id) continue;            // not the start of a run
+    const int64_t o = ((int64_t)id * per_row + c) * VEC;
+    float w[VEC], a[VEC], g[VEC];
+    if (VEC == 4) {
+      const float4 w4 = *reinterpret_cast<const float4 *>(table + o), a4 = *reinterpret_cast<const float4 *>(accum + o);
+      w[0] = w4.x; w[1 % VEC] = w4.y; w[2 % VEC] = w4.z; w[3 % VEC] = w4.w;
+      a[0] = a4.x; a[1 % VEC] = a4.y; a[2 % VEC] = a4.z; a[3 % VEC] = a4.w;
+    } else {
+      w[0] = table[o];
+      a[0] = accum[o];
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) g[v] = 0.f;
+    // the run's first position, then eight positions per round: their gradient pieces are independent loads (a
+    // position beyond the run re-reads the first piece and is dropped), added in occurrence order -- one memory latency
+    // per eight duplicates instead of one per duplicate
+    auto piece = [&](int64_t pos, float (&r)[VEC]) __attribute__((always_inline)) {
+      const int64_t src = perm[pos];
+      if (VEC == 4) {
+        const float4 e = reinterpret_cast<const float4 *>(grad_out)[src * per_row + c];
+        r[0] = e.x; r[1 % VEC] = e.y; r[2 % VEC] = e.z; r[3 % VEC] = e.w;
+      } else {
+        r[0] = grad_out[src * per_row + c];
+      }
+    };
+    {
+      float r[VEC];
+      piece(i, r);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) g[v] += r[v];
+    }
+    for (int64_t p = i + 1; p < n && sorted_ids[p] == id; p += 8) {
+      float r[8][VEC];
+      bool in_run[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        in_run[u] = p + u < n && sorted_ids[p + u < n ? p + u : p] == id;
+        piece(in_run[u] ? p + u : i, r[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (in_run[u]) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) g[v] += r[u][v];
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const ClippyElement e = clippy_element(w[v], a[v], g[v], h);
+      if (APPLY) clippy_apply(e, g[v], factor, h, w[v], a[v]);
+      else m = clippy_min_scale(m, e);
+    }
+    if (APPLY) {
+      if (VEC == 4) {
+        *reinterpret_cast<float4 *>(table + o) = make_float4(w[0], w[1 % VEC], w[2 % VEC], w[3 % VEC]);
+        *reinterpret_cast<float4 *>(accum + o) = make_float4(a[0], a[1 % VEC], a[2 % VEC], a[3 % VEC]);
+      } else {
+        table[o] = w[0];
+        accum[o] = a[0];
+      }
+    }
+  }
+  if (!APPLY) {
+    m = clippy_wave_min(m);
+    if ((threadIdx.x & 63) == 0) clippy_factor_min(factor_slot, m);
+  }
+}
+
+template <typename IdT, bool APPLY>
+__global__ void __launch_bounds__(256) clippy_rowscan_kernel(
+    const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d, int64_t vocab,
+    float *__restrict__ table, float *__restrict__ accum, float *__restrict__ factor_slot, const ClippyHyper h) {
+  __shared__ int32_t s_ids[kRowscanChunk];
+  __shared__ int s_hits[4 * kRowscanHitCap];
+  constexpr int PASS = APPLY ? 2 : 1;
+  if (d <= 64) scatter_rowscan_body_ns<IdT, 1, PASS>(grad_out, ids, n, d, vocab, table, accum, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, factor_slot, &h);
+  else if (d <= 128) scatter_rowscan_body_ns<IdT, 2, PASS>(grad_out, ids, n, d, vocab, table, accum, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, factor_slot, &h);
+  else scatter_rowscan_body_ns<IdT, 4, PASS>(grad_out, ids, n, d, vocab, table, accum, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, factor_slot, &h);
+}
+
+}  // namespace tfrs
+
+extern "C" size_t tfrs_clippy_sparse_workspace_bytes(int64_t n, int rowscan) {
+  return rowscan ? 256 : tfrs_embedding_scatter_add_workspace_bytes(n);
+}
+
+extern "C" int tfrs_clippy_sparse(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d,
+                                  int64_t vocab, float *table, float *accum, float *factor, float lr, float eps,
+                                  float var_rel, float acc_rel, float abs_thr, int mode, int rowscan,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  using namespace tfrs;
+  TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "clippy_sparse: bad shape");
+  TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll, "clippy_sparse: vocab / n must fit 32 bits");
+  TFRS_CHECK_ARG(table && accum && factor, "clippy_sparse: NULL pointer");
+  TFRS_CHECK_ARG(mode >= 0 && mode <= 2, "clippy_sparse: mode must be 0 (delayed), 1 (delayed, clipped) or 2 (standard)");
+  TFRS_CHECK_ARG(var_rel >= 0.f && acc_rel >= 0.f && abs_thr >= 0.f, "clippy_sparse: thresholds must be non-negative");
+  TFRS_CHECK_ARG(!rowscan || d <= 256, "clippy_sparse: d=%d > 256 on the row-scan route (use the sorted route)", d);
+  hipStream_t s = (hipStream_t)stream;
+  const ClippyHyper h = {lr, eps, var_rel, acc_rel, abs_thr, mode};
+  hipLaunchKernelGGL(clippy_arm_kernel, dim3(1), dim3(64), 0, s, factor, 1);
+  if (n == 0) {     // factor 1, nothing written
+    TFRS_LAUNCH_CHECK();
+    return TFRS_OK;
+  }
+  TFRS_CHECK_ARG(grad_out && ids, "clippy_sparse: NULL pointer");
+  if (rowscan) {
+    const dim3 grid((unsigned)((vocab + 3) / 4)), block(256);
+    if (ids_are_i64) {
+      hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, false>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
+      hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, true>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
+    } else {
+      hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, false>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
+      hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, true>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
+    }
+    TFRS_LAUNCH_CHECK();
+    return TFRS_OK;
+  }
+  TFRS_CHECK_ARG(workspace, "clippy_sparse: NULL workspace");
+  if (workspace_bytes < tfrs_embedding_scatter_add_workspace_bytes(n)) {
+    set_error("clippy_sparse: workspace too small");
+    return TFRS_ENOMEM;
+  }
+  uint32_t *keys[2], *vals[2];
+  const int cur = sort_id_positions(ids, ids_are_i64, n, vocab, workspace, s, keys, vals);
+  TFRS_LAUNCH_CHECK();
+  const bool vec = (d % 4 == 0) && (((uintptr_t)grad_out) % 16 == 0) && (((uintptr_t)table) % 16 == 0) &&
+                   (((uintptr_t)accum) % 16 == 0);
+  const int64_t total = n * (vec ? d / 4 : d);
+  const dim3 grid(grid_for(total, 256 * 64)), block(256);
+  if (vec) {
+    hipLaunchKernelGGL((clippy_sorted_kernel<4, false>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
+    hipLaunchKernelGGL((clippy_sorted_kernel<4, true>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
+  } else {
+    hipLaunchKernelGGL((clippy_sorted_kernel<1, false>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
+    hipLaunchKernelGGL((clippy_sorted_kernel<1, true>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
+  }
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }

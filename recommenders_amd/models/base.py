@@ -39,6 +39,7 @@ class Model(torch.nn.Module):
     self._process_group = process_group
     self._sync_gradients = sync_gradients
     self._bucket_bytes = int(bucket_bytes)
+    self._optimizer_validated = False    # (an optimizer's `validate` hook runs before the first step)
     self.invalidate_captured_steps()     # captured steps belong to the configuration they were captured under
 
   # data-parallel gradient exchange ------------------------------------------------------
@@ -200,6 +201,13 @@ class Model(torch.nn.Module):
     if self.optimizer is None:
       raise RuntimeError("Call `compile(optimizer=...)` before training.")
     self.train()
+    if not getattr(self, "_optimizer_validated", False):
+      # an optimizer that covers parameter subsets (experimental.optimizers.CompositeOptimizer) is told the model's
+      # trainable parameters once, so that one no member handles is an error and not a silently untrained weight
+      validate = getattr(self.optimizer, "validate", None)
+      if callable(validate):
+        validate([p for p in self.parameters() if p.requires_grad])
+      self._optimizer_validated = True
     self.optimizer.zero_grad(set_to_none=True)
     # (under capture the metric update of the task runs as a parallel branch of the graph, _streams.py; it reads the
     # embedding tables, so it is joined in front of the optimizer step that rewrites them)
@@ -297,6 +305,12 @@ class Model(torch.nn.Module):
       had_state = [(t, t.detach().clone()) for st in self.optimizer.state.values()
                    for t in st.values() if isinstance(t, torch.Tensor)]
     can_roll_back = bool(had_state) or callable(getattr(self.optimizer, "reset_state_", None))
+    # an optimizer made of several (experimental.optimizers.CompositeOptimizer) decides member by member and answers
+    # with one roll-back for all of them, or None: then nothing is rolled back, as for a plain torch.optim optimizer
+    member_roll_back = None
+    if training and callable(getattr(self.optimizer, "capture_rollback", None)):
+      member_roll_back = self.optimizer.capture_rollback()
+      can_roll_back = member_roll_back is not None
     metric_before = [(t, t.detach().clone()) for t in self._metric_state_tensors()]
     known = {(t.data_ptr(), tuple(t.shape), t.dtype) for t, _ in metric_before}
     # module buffers (BatchNorm running statistics, step counters) and the device's random stream are
@@ -313,7 +327,9 @@ class Model(torch.nn.Module):
         if training and can_roll_back:
           for p, v in zip(params, saved_params):
             p.copy_(v)
-          if had_state:
+          if member_roll_back is not None:
+            member_roll_back()
+          elif had_state:
             for t, v in had_state:
               t.copy_(v)
           else:
@@ -414,8 +430,9 @@ class Model(torch.nn.Module):
     """``graph=None`` (default): replay captured steps when that is known to be safe -- a ROCm device,
     no gradient exchange (a collective inside a capture is not supported here), and for training an
     optimizer whose step has no host-side state that changes from step to step: this package's
-    ``Adagrad``, or a ``torch.optim`` optimizer built with ``capturable=True`` (a host-side step
-    counter or learning-rate schedule would be frozen into the graph at capture time).
+    ``Adagrad`` and ``experimental.optimizers.ClippyAdagrad``, a ``torch.optim`` optimizer built with
+    ``capturable=True`` (a host-side step counter or learning-rate schedule would be frozen into the graph at
+    capture time), or a ``CompositeOptimizer`` of such members.
     ``graph=True`` forces it, ``graph=False`` / ``TFRS_FIT_GRAPH=0`` keeps every step eager."""
     import os
     if graph is False or os.environ.get("TFRS_FIT_GRAPH", "1") == "0":
@@ -430,10 +447,17 @@ class Model(torch.nn.Module):
     if graph is True or not training:
       return True
     from recommenders_amd import optimizers as own
+    from recommenders_amd.experimental.optimizers import ClippyAdagrad, CompositeOptimizer
+
+    def capturable(opt) -> bool:
+      if isinstance(opt, (own.Adagrad, ClippyAdagrad)):
+        return True
+      return bool(opt.param_groups) and all(g.get("capturable", False) for g in opt.param_groups)
+
     opt = self.optimizer
-    if isinstance(opt, own.Adagrad):
-      return True
-    return bool(opt.param_groups) and all(g.get("capturable", False) for g in opt.param_groups)
+    if isinstance(opt, CompositeOptimizer):
+      return all(capturable(member) for member in opt.optimizers)
+    return capturable(opt)
 
   def invalidate_captured_steps(self) -> None:
     """Drops every step `fit` / `evaluate` captured (and the private memory pools of their graphs).

@@ -47,16 +47,16 @@ def _adagrad_dense_multi(items, lr: float, eps: float, mode: int) -> None:
     torch.autograd.graph.increment_version(p)
 
 
-class Adagrad(torch.optim.Optimizer):
-  """``tf.keras.optimizers.Adagrad(learning_rate, initial_accumulator_value, epsilon)``."""
+class SliceOwningOptimizer(torch.optim.Optimizer):
+  """What every optimizer of this package that takes the ``(ids, rows)`` slices of embedding lookups shares
+  (``Adagrad``, ``experimental.optimizers.ClippyAdagrad``): ownership of the tables' sparse-gradient mode
+  (``_tfrs_sparse_grad`` / ``_tfrs_slices`` / ``_tfrs_sparse_owner``), ``close``, the per-parameter accumulator,
+  ``reset_state_``, ``zero_grad`` and the version bumps after raw-pointer writes.  Subclasses pass their
+  hyper-parameters as ``defaults`` (``initial_accumulator_value`` among them) and implement ``step``."""
 
-  def __init__(self, params: Iterable, learning_rate: float = 0.001,
-               initial_accumulator_value: float = 0.1, epsilon: float = 1e-7, legacy: bool = False):
-    if initial_accumulator_value < 0.0:
+  def __init__(self, params: Iterable, defaults: dict):
+    if defaults["initial_accumulator_value"] < 0.0:
       raise ValueError("initial_accumulator_value must be non-negative")
-    defaults = dict(learning_rate=float(learning_rate),
-                    initial_accumulator_value=float(initial_accumulator_value),
-                    epsilon=float(epsilon), legacy=bool(legacy))
     super().__init__(params, defaults)
     for group in self.param_groups:
       for p in group["params"]:
@@ -122,6 +122,30 @@ class Adagrad(torch.optim.Optimizer):
         if getattr(p, "_tfrs_sparse_grad", False):
           p._tfrs_slices.clear()
 
+  @staticmethod
+  def _merged_slices(p):
+    """The pending slices of table ``p`` as one ``(ids, rows)`` pair (``None`` when there are none); clears them."""
+    slices = getattr(p, "_tfrs_slices", None)
+    if not slices:
+      return None
+    if len(slices) == 1:
+      ids, rows = slices[0]
+    else:   # the same table looked up several times: one combined IndexedSlices
+      ids = torch.cat([s[0].reshape(-1) for s in slices])
+      rows = torch.cat([s[1].reshape(-1, p.shape[1]) for s in slices])
+    slices.clear()
+    return ids, rows
+
+
+class Adagrad(SliceOwningOptimizer):
+  """``tf.keras.optimizers.Adagrad(learning_rate, initial_accumulator_value, epsilon)``."""
+
+  def __init__(self, params: Iterable, learning_rate: float = 0.001,
+               initial_accumulator_value: float = 0.1, epsilon: float = 1e-7, legacy: bool = False):
+    super().__init__(params, dict(learning_rate=float(learning_rate),
+                                  initial_accumulator_value=float(initial_accumulator_value),
+                                  epsilon=float(epsilon), legacy=bool(legacy)))
+
   @torch.no_grad()
   def step(self, closure=None):
     loss = None
@@ -134,16 +158,11 @@ class Adagrad(torch.optim.Optimizer):
       touched = []
       for p in group["params"]:
         acc = self._accumulator(p, group["initial_accumulator_value"])
-        slices = getattr(p, "_tfrs_slices", None)
-        if slices:
-          if len(slices) == 1:
-            ids, rows = slices[0]
-          else:   # the same table looked up several times: one combined IndexedSlices
-            ids = torch.cat([s[0].reshape(-1) for s in slices])
-            rows = torch.cat([s[1].reshape(-1, p.shape[1]) for s in slices])
+        merged = self._merged_slices(p)
+        if merged is not None:
+          ids, rows = merged
           sparse.append((p.data, acc, rows, ids))
           touched.append(p)
-          slices.clear()
       if sparse:
         emb.adagrad_sparse_update_multi_(sparse, lr, eps, legacy)   # small tables: one launch for all
         # the kernels wrote through raw pointers: bump the version counters so that anything
