@@ -416,6 +416,37 @@ size_t tfrs_clippy_sparse_workspace_bytes(int64_t n, int rowscan);
 int tfrs_clippy_sparse(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d, int64_t vocab,
                        float *table, float *accum, float *factor, float lr, float eps, float var_rel, float acc_rel,
                        float abs_thr, int mode, int rowscan, void *workspace, size_t workspace_bytes, void *stream);
+/* optimizers.SGD / Adam / Ftrl (tf.keras.optimizers.SGD, Adam and Ftrl; on tables: row-sparse, Adam lazily, as
+ * tf.tpu.experimental.embedding.Adam(lazy_adam=True) and ResourceSparseApplyFtrlV2), f32 in the written order, no
+ * contraction.  rule 0 = SGD, 1 = Adam, 2 = Ftrl; hyper_h is a HOST array of 8 floats:
+ *   SGD   {lr}:                          w -= lr * g
+ *   Adam  {1 - beta_1, 1 - beta_2, epsilon}, slots m, v; alpha is the DEVICE float that tfrs_adam_tick wrote:
+ *         m += (g - m) * (1 - beta_1);  v += (g * g - v) * (1 - beta_2);  w -= m * alpha / (sqrt(v) + epsilon)
+ *   Ftrl  {lr, l1, 2 * (l2 + beta / (2 lr)), 2 * l2_shrinkage, learning_rate_power}, slots n (accumulator), lin (linear);
+ *         learning_rate_power is -0.5 (n^p = sqrt(n)) or 0 (n^p = 1):
+ *         g' = g + 2 shrink w;  n' = n + g * g;  lin += g' - (n'^p - n^p) / lr * w;  q = n'^p / lr + 2 l2r;
+ *         w = (clip(lin, -l1, l1) - lin) / q;  n = n'
+ * _sparse: the looked-up rows of table[vocab, d] (and of slot0 / slot1 of the same shape; NULL for SGD) from UNSORTED
+ * ids (int32 / int64) and grad_out[n, d]: duplicates are summed first, in occurrence order from +0 (on the sorted route a run
+ * longer than a piece of max(32, pow2 >= d) positions is cut at fixed positions into occurrence-order pieces that are
+ * then added in order, as the sparse Adagrad update does) -- the bits
+ * of tfrs_embedding_scatter_add_unsorted's sums; ids outside [0, vocab) are ignored; a touched row whose sum is zero is
+ * still updated; untouched rows are not written.  rowscan != 0: the sort-free row scan (d <= 256), else radix sort +
+ * segments with workspace from tfrs_table_update_workspace_bytes(n, rowscan).  n == 0: nothing is written.
+ * _dense_multi: up to 32 tensors in one launch, host arrays of device pointers as in tfrs_adagrad_dense_multi (the slot
+ * arrays may be NULL for SGD).
+ * tfrs_adam_tick: one thread; *step += advance (0 or 1; step is a device int64, Keras's iterations + 1 after the add),
+ * *alpha = (float)(lr * sqrt(1 - beta_2^t) / (1 - beta_1^t)) computed in float64 from the integer t.  On the device, so
+ * that a captured step replays with a live counter.  Every argument check comes before any device call. */
+size_t tfrs_table_update_workspace_bytes(int64_t n, int rowscan);
+int tfrs_table_update_sparse(int rule, const float *hyper_h, const float *alpha, const float *grad_out, const void *ids,
+                             int ids_are_i64, int64_t n, int d, int64_t vocab, float *table, float *slot0, float *slot1,
+                             int rowscan, void *workspace, size_t workspace_bytes, void *stream);
+int tfrs_table_update_dense_multi(int rule, const float *hyper_h, const float *alpha, int ntensors,
+                                  float *const *params_h, float *const *slot0_h, float *const *slot1_h,
+                                  const float *const *grads_h, const int64_t *n_h, void *stream);
+int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2, int advance,
+                   void *stream);
 /* Up to 16 device buffers copied in ONE launch: a batch's input tensors into the static buffers of a captured
  * train / test step (the `Model.fit` loop of models/base.py:64-85 replays HIP graphs; README.md:84-98).  Host arrays of
  * device pointers and byte counts; buffers must not overlap. */

@@ -91,6 +91,10 @@ SIGNATURES = {
     "tfrs_clippy_sparse_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "tfrs_clippy_sparse": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, P, c_float, c_float, c_float, c_float,
                                    c_float, c_int, c_int, P, c_size_t, P]),
+    "tfrs_table_update_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "tfrs_table_update_sparse": (c_int, [c_int, P, P, P, P, c_int, c_i64, c_int, c_i64, P, P, P, c_int, P, c_size_t, P]),
+    "tfrs_table_update_dense_multi": (c_int, [c_int, P, P, c_int, P, P, P, P, P, P]),
+    "tfrs_adam_tick": (c_int, [P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, P]),
     "tfrs_copy_multi": (c_int, [c_int, P, P, P, P]),
     "tfrs_embedding_scatter_add_rowscan": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, c_float,
                                                    c_float, c_int, P]),

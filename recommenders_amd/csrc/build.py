@@ -33,6 +33,7 @@ SOURCES = [
     "dedup.hip",
     "embedding.hip",
     "clippy.hip",
+    "table_update.hip",
     "shard_route.hip",
     "hashing.hip",
     "softmax.hip",

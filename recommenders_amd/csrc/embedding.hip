@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "clippy.h"
+#include "table_rules.h"
 
 namespace tfrs {
 
@@ -326,12 +327,14 @@ constexpr int kRowscanHitCap = 128;
 // compiler, which then waits for each one (the ISA of the runtime-d version: 176 loads, at most ONE in flight).
 // CLIPPY: 0 = the scatter-add / Adagrad epilogue; 1 / 2 = the factor / apply pass of ClippyAdagrad on the touched rows
 // (clippy_rowscan_kernel below: the same scan and the same occurrence-order sums, another epilogue).
-template <typename IdT, int NS, int CLIPPY = 0>
+// RULE: void, or an update rule of table_rules.h (table_update_rowscan_kernel below): the touched rows of dst, accum (the
+// rule's first slot) and slot1 go through rule->apply, untouched rows are not written.
+template <typename IdT, int NS, int CLIPPY = 0, typename RULE = void>
 __device__ __forceinline__ void scatter_rowscan_body_ns(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d,
     int64_t vocab, float *__restrict__ dst, float *__restrict__ accum, float lr, float eps,
     int adagrad, int64_t block, int32_t *s_ids, int *s_hits, float *__restrict__ factor_slot = nullptr,
-    const ClippyHyper *clippy = nullptr) {
+    const ClippyHyper *clippy = nullptr, const RULE *rule = nullptr, float *__restrict__ slot1 = nullptr) {
   // the id list goes through LDS in chunks shared by the workgroup's 4 rows, so a wave's scan
   // is 64 LDS reads per 4096 ids instead of 64 dependent global loads
   constexpr int kChunk = kRowscanChunk;
@@ -409,6 +412,27 @@ __device__ __forceinline__ void scatter_rowscan_body_ns(
       __builtin_amdgcn_wave_barrier();
     }
     flush();
+  }
+  if constexpr (!std::is_void<RULE>::value) {
+    if (row_ok && touched) {   // wave-uniform
+      float pv[NS], s0[NS], s1[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        pv[s] = dst[v * d + fo[s]];
+        s0[s] = RULE::kSlots >= 1 ? accum[v * d + fo[s]] : 0.0f;
+        s1[s] = RULE::kSlots >= 2 ? slot1[v * d + fo[s]] : 0.0f;
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (fok[s]) {
+          rule->apply(g[s], pv[s], s0[s], s1[s]);
+          dst[v * d + fo[s]] = pv[s];
+          if (RULE::kSlots >= 1) accum[v * d + fo[s]] = s0[s];
+          if (RULE::kSlots >= 2) slot1[v * d + fo[s]] = s1[s];
+        }
+      }
+    }
+    return;
   }
   if (CLIPPY) {
     const float factor = CLIPPY == 2 ? *factor_slot : 1.0f;
@@ -1427,4 +1451,186 @@ extern "C" int tfrs_clippy_sparse(const float *grad_out, const void *ids, int id
   }
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
+}
+
+// ---- optimizers.SGD / Adam / Ftrl on the looked-up rows of a table (table_rules.h) ----------------------------------
+// The sparse Adagrad update with the arithmetic taken out: the same sort, the same piece-wise sums of long runs
+// (scatter_add_pieces_kernel), the same two rounds of independent loads, the same row scan for small tables -- the rule
+// is a template parameter, so the kernels below exist once.  A run's summed gradient is bit for bit the one of
+// scatter_add_u32_kernel / scatter_rowscan_body_ns (the same loads added in the same order from +0); a touched row
+// whose sum is exactly zero is still updated (Adam's moments decay, Ftrl re-solves the row).
+namespace tfrs {
+
+template <typename RULE, int VEC, bool NT>
+__global__ void __launch_bounds__(256) table_update_sorted_kernel(
+    const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids, const uint32_t *__restrict__ perm,
+    int64_t n, int d, uint32_t vocab, float *__restrict__ table, float *__restrict__ slot0, float *__restrict__ slot1,
+    const RULE rule, int piece, const float *__restrict__ part) {
+  const int per_row = d / VEC;
+  const int64_t total = n * per_row;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / per_row;
+    const int c = (int)(t - i * per_row);
+    // round one: {id, its neighbours, the position}; round two: {gradient piece, weights, slots}
+    const uint32_t id = sorted_ids[i];
+    const uint32_t id_prev = sorted_ids[i > 0 ? i - 1 : 0];          // (clamped: the loads are unconditional)
+    const uint32_t id_next = sorted_ids[i + 1 < n ? i + 1 : n - 1];
+    const int64_t src0 = perm[i];
+    if (id >= vocab) continue;                       // invalid / padding id: can never write
+    if (i > 0 && id_prev == id) continue;            // not the start of a run
+    const int64_t o = ((int64_t)id * per_row + c) * VEC;
+    float w[VEC], s0[VEC], s1[VEC], g[VEC];
+    auto load = [&](const float *p, float (&r)[VEC], bool nt) __attribute__((always_inline)) {
+      if (VEC == 4) {
+        const float4 e = nt ? nt_load4(reinterpret_cast<const float4 *>(p)) : *reinterpret_cast<const float4 *>(p);
+        r[0] = e.x; r[1 % VEC] = e.y; r[2 % VEC] = e.z; r[3 % VEC] = e.w;
+      } else {
+        r[0] = *p;
+      }
+    };
+    auto store = [&](float *p, const float (&r)[VEC]) __attribute__((always_inline)) {
+      if (VEC == 4) {
+        const float4 e = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
+        if (NT) nt_store4(e, reinterpret_cast<float4 *>(p));
+        else *reinterpret_cast<float4 *>(p) = e;
+      } else {
+        *p = r[0];
+      }
+    };
+    load(table + o, w, NT);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) s0[v] = s1[v] = 0.f;
+    if (RULE::kSlots >= 1) load(slot0 + o, s0, NT);
+    if (RULE::kSlots >= 2) load(slot1 + o, s1, NT);
+    {
+      float r[VEC];
+      load(grad_out + (src0 * per_row + c) * VEC, r, NT);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) g[v] = 0.f + r[v];     // (the sum of a run starts from +0, -0 gradients included)
+    }
+    // the run's first piece: up to the first multiple of `piece` that is >= i + piece ...
+    int64_t p = i + 1;
+    const int64_t first_end = ((i + piece - 1) / piece + 1) * (int64_t)piece;
+    if (p < n && id_next == id) {
+      for (; p < n && p < first_end && sorted_ids[p] == id; ++p) {
+        float r[VEC];
+        load(grad_out + ((int64_t)perm[p] * per_row + c) * VEC, r, false);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) g[v] += r[v];
+      }
+    }
+    // ... then the partial sums of the pieces that continue it (scatter_add_pieces_kernel)
+    if (p == first_end) {
+      for (int64_t b = first_end / piece; b * piece < n && sorted_ids[b * piece] == id; ++b) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) g[v] += part[((b - 1) * per_row + c) * VEC + v];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) rule.apply(g[v], w[v], s0[v], s1[v]);
+    store(table + o, w);
+    if (RULE::kSlots >= 1) store(slot0 + o, s0);
+    if (RULE::kSlots >= 2) store(slot1 + o, s1);
+  }
+}
+
+template <typename RULE, typename IdT>
+__global__ void __launch_bounds__(256) table_update_rowscan_kernel(
+    const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d, int64_t vocab,
+    float *__restrict__ table, float *__restrict__ slot0, float *__restrict__ slot1, const RULE rule) {
+  __shared__ int32_t s_ids[kRowscanChunk];
+  __shared__ int s_hits[4 * kRowscanHitCap];
+  if (d <= 64) scatter_rowscan_body_ns<IdT, 1, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
+  else if (d <= 128) scatter_rowscan_body_ns<IdT, 2, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
+  else scatter_rowscan_body_ns<IdT, 4, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
+}
+
+struct SparseUpdateArgs {
+  const float *grad_out;
+  const void *ids;
+  int ids_are_i64;
+  int64_t n;
+  int d;
+  int64_t vocab;
+  float *table, *slot0, *slot1;
+  int rowscan;
+  void *workspace;
+  hipStream_t stream;
+};
+
+template <typename RULE>
+static int table_update_sparse_launch(const SparseUpdateArgs &a, const RULE &rule) {
+  hipStream_t s = a.stream;
+  const dim3 block(256);
+  if (a.rowscan) {
+    const dim3 grid((unsigned)((a.vocab + 3) / 4));
+    if (a.ids_are_i64)
+      hipLaunchKernelGGL((table_update_rowscan_kernel<RULE, int64_t>), grid, block, 0, s, a.grad_out, a.ids, a.n, a.d, a.vocab, a.table, a.slot0, a.slot1, rule);
+    else
+      hipLaunchKernelGGL((table_update_rowscan_kernel<RULE, int32_t>), grid, block, 0, s, a.grad_out, a.ids, a.n, a.d, a.vocab, a.table, a.slot0, a.slot1, rule);
+    TFRS_LAUNCH_CHECK();
+    return TFRS_OK;
+  }
+  uint32_t *keys[2], *vals[2];
+  const int cur = sort_id_positions(a.ids, a.ids_are_i64, a.n, a.vocab, a.workspace, s, keys, vals);
+  TFRS_LAUNCH_CHECK();
+  const bool vec = (a.d % 4 == 0) && (((uintptr_t)a.grad_out | (uintptr_t)a.table | (uintptr_t)a.slot0 | (uintptr_t)a.slot1) % 16 == 0);
+  const int64_t total = a.n * (vec ? a.d / 4 : a.d);
+  const dim3 grid(grid_for(total, 256 * 64));
+  // (pieces as in tfrs_embedding_scatter_add_unsorted: their partial sums fit the sort's free ping-pong key buffer)
+  int piece = 32;
+  while (piece < a.d) piece *= 2;
+  float *part = reinterpret_cast<float *>(keys[cur ^ 1]);
+  const int64_t ptotal = ((a.n + piece - 1) / piece) * (vec ? a.d / 4 : a.d);
+  const dim3 pgrid(grid_for(ptotal, 256 * 64));
+  const uint32_t vocab = (uint32_t)a.vocab;
+  if (vec) {
+    hipLaunchKernelGGL((scatter_add_pieces_kernel<4>), pgrid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, piece, part);
+    // the non-temporal row streams above the table size measured for Adagrad (TFRS_SCATTER_NT=0 switches them off)
+    const char *nte = option("TFRS_SCATTER_NT");
+    if (a.vocab * (int64_t)a.d * 4 > (1ll << 30) && !(nte && nte[0] == '0'))
+      hipLaunchKernelGGL((table_update_sorted_kernel<RULE, 4, true>), grid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, a.table, a.slot0, a.slot1, rule, piece, part);
+    else
+      hipLaunchKernelGGL((table_update_sorted_kernel<RULE, 4, false>), grid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, a.table, a.slot0, a.slot1, rule, piece, part);
+  } else {
+    hipLaunchKernelGGL((scatter_add_pieces_kernel<1>), pgrid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, piece, part);
+    hipLaunchKernelGGL((table_update_sorted_kernel<RULE, 1, false>), grid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, a.table, a.slot0, a.slot1, rule, piece, part);
+  }
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+}  // namespace tfrs
+
+extern "C" size_t tfrs_table_update_workspace_bytes(int64_t n, int rowscan) {
+  return rowscan ? 256 : tfrs_embedding_scatter_add_workspace_bytes(n);
+}
+
+extern "C" int tfrs_table_update_sparse(int rule, const float *hyper_h, const float *alpha, const float *grad_out,
+                                        const void *ids, int ids_are_i64, int64_t n, int d, int64_t vocab, float *table,
+                                        float *slot0, float *slot1, int rowscan, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+  using namespace tfrs;
+  int rc = table_rule_check("table_update_sparse", rule, hyper_h, alpha);
+  if (rc != TFRS_OK) return rc;
+  TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "table_update_sparse: bad shape");
+  TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll, "table_update_sparse: vocab / n must fit 32 bits");
+  TFRS_CHECK_ARG(table && (rule == kRuleSgd || (slot0 && slot1)), "table_update_sparse: NULL pointer");
+  TFRS_CHECK_ARG(!rowscan || d <= 256, "table_update_sparse: d=%d > 256 on the row-scan route (use the sorted route)", d);
+  if (n == 0) return TFRS_OK;     // nothing is written
+  TFRS_CHECK_ARG(grad_out && ids, "table_update_sparse: NULL pointer");
+  if (!rowscan) {
+    TFRS_CHECK_ARG(workspace, "table_update_sparse: NULL workspace");
+    if (workspace_bytes < tfrs_embedding_scatter_add_workspace_bytes(n)) {
+      set_error("table_update_sparse: workspace too small");
+      return TFRS_ENOMEM;
+    }
+  }
+  const SparseUpdateArgs a = {grad_out, ids, ids_are_i64, n, d, vocab, table, slot0, slot1, rowscan, workspace,
+                              (hipStream_t)stream};
+  if (rule == kRuleSgd) return table_update_sparse_launch(a, SgdRule{hyper_h[0]});
+  if (rule == kRuleAdam) return table_update_sparse_launch(a, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha});
+  if (hyper_h[4] != 0.0f) return table_update_sparse_launch(a, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]});
+  return table_update_sparse_launch(a, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]});
 }

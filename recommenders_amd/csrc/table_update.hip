@@ -1,0 +1,137 @@
+// optimizers.SGD / Adam / Ftrl on dense parameters (one launch for up to 32 tensors, the layout of
+// adagrad_dense_multi_kernel with the rule of table_rules.h as a template parameter) and Adam's device-side step
+// counter.  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
+#include "common.h"
+#include "table_rules.h"
+
+namespace tfrs {
+
+struct DenseUpdateTensors {
+  int ntensors;
+  int first_block[33];
+  float *p[32];
+  float *s0[32];
+  float *s1[32];
+  const float *g[32];
+  int64_t n[32];
+};
+constexpr int kDenseUpdatePerBlock = 256 * 16;
+
+// tensor t owns blocks [first_block[t], first_block[t + 1]) of 256 threads x 4 x float4; a tensor that is not 16-byte
+// aligned, and the block in which a tensor ends, take the scalar loop
+template <typename RULE>
+__global__ void __launch_bounds__(256) table_update_dense_multi_kernel(const DenseUpdateTensors t, const RULE rule) {
+  int k = 0;
+  while (k + 1 < t.ntensors && (int)blockIdx.x >= t.first_block[k + 1]) ++k;
+  float *__restrict__ p = t.p[k];
+  float *__restrict__ s0 = t.s0[k];
+  float *__restrict__ s1 = t.s1[k];
+  const float *__restrict__ g = t.g[k];
+  const int64_t n = t.n[k];
+  const int64_t base = (int64_t)((int)blockIdx.x - t.first_block[k]) * kDenseUpdatePerBlock;
+  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(s0) | reinterpret_cast<uintptr_t>(s1) |
+                     reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  if (vec && base + kDenseUpdatePerBlock <= n) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 gv[4], pv[4], av[4], bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = base + (int64_t)(u * 256 + threadIdx.x) * 4;
+      gv[u] = *reinterpret_cast<const float4 *>(g + i);
+      pv[u] = *reinterpret_cast<const float4 *>(p + i);
+      av[u] = RULE::kSlots >= 1 ? *reinterpret_cast<const float4 *>(s0 + i) : zero;
+      bv[u] = RULE::kSlots >= 2 ? *reinterpret_cast<const float4 *>(s1 + i) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = base + (int64_t)(u * 256 + threadIdx.x) * 4;
+      rule.apply(gv[u].x, pv[u].x, av[u].x, bv[u].x);
+      rule.apply(gv[u].y, pv[u].y, av[u].y, bv[u].y);
+      rule.apply(gv[u].z, pv[u].z, av[u].z, bv[u].z);
+      rule.apply(gv[u].w, pv[u].w, av[u].w, bv[u].w);
+      *reinterpret_cast<float4 *>(p + i) = pv[u];
+      if (RULE::kSlots >= 1) *reinterpret_cast<float4 *>(s0 + i) = av[u];
+      if (RULE::kSlots >= 2) *reinterpret_cast<float4 *>(s1 + i) = bv[u];
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < n && i < base + kDenseUpdatePerBlock; i += 256) {
+    float w = p[i], a = RULE::kSlots >= 1 ? s0[i] : 0.f, b = RULE::kSlots >= 2 ? s1[i] : 0.f;
+    rule.apply(g[i], w, a, b);
+    p[i] = w;
+    if (RULE::kSlots >= 1) s0[i] = a;
+    if (RULE::kSlots >= 2) s1[i] = b;
+  }
+}
+
+template <typename RULE>
+static int table_update_dense_launch(const DenseUpdateTensors &t, int64_t blocks, const RULE &rule, hipStream_t s) {
+  hipLaunchKernelGGL((table_update_dense_multi_kernel<RULE>), dim3((unsigned)blocks), dim3(256), 0, s, t, rule);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+// One thread: t += advance;  alpha = lr * sqrt(1 - beta_2^t) / (1 - beta_1^t) in float64 from the integer t (powers by
+// repeated squaring: at most 2 * 63 products), rounded once to f32.  t is Keras's iterations + 1.
+__global__ void adam_tick_kernel(int64_t *__restrict__ step, float *__restrict__ alpha, double lr, double beta_1,
+                                 double beta_2, int advance) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t t = *step + advance;
+  if (advance) *step = t;
+  double p1 = 1.0, p2 = 1.0, b1 = beta_1, b2 = beta_2;
+  for (int64_t e = t; e > 0; e >>= 1) {
+    if (e & 1) {
+      p1 *= b1;
+      p2 *= b2;
+    }
+    b1 *= b1;
+    b2 *= b2;
+  }
+  *alpha = (float)(lr * sqrt(1.0 - p2) / (1.0 - p1));
+}
+
+}  // namespace tfrs
+
+using namespace tfrs;
+
+extern "C" int tfrs_table_update_dense_multi(int rule, const float *hyper_h, const float *alpha, int ntensors,
+                                             float *const *params_h, float *const *slot0_h, float *const *slot1_h,
+                                             const float *const *grads_h, const int64_t *n_h, void *stream) {
+  int rc = table_rule_check("table_update_dense_multi", rule, hyper_h, alpha);
+  if (rc != TFRS_OK) return rc;
+  TFRS_CHECK_ARG(ntensors >= 1 && ntensors <= 32, "table_update_dense_multi: 1..32 tensors");
+  TFRS_CHECK_ARG(params_h && grads_h && n_h && (rule == kRuleSgd || (slot0_h && slot1_h)),
+                 "table_update_dense_multi: NULL argument array");
+  DenseUpdateTensors t = {};
+  t.ntensors = ntensors;
+  int64_t blocks = 0;
+  for (int i = 0; i < ntensors; ++i) {
+    TFRS_CHECK_ARG(n_h[i] >= 0 && (n_h[i] == 0 || (params_h[i] && grads_h[i] &&
+                                                   (rule == kRuleSgd || (slot0_h[i] && slot1_h[i])))),
+                   "table_update_dense_multi: bad tensor %d", i);
+    t.first_block[i] = (int)blocks;
+    blocks += (n_h[i] + kDenseUpdatePerBlock - 1) / kDenseUpdatePerBlock;
+    TFRS_CHECK_ARG(blocks < (1ll << 31), "table_update_dense_multi: too many elements for one launch");
+    t.p[i] = params_h[i]; t.g[i] = grads_h[i]; t.n[i] = n_h[i];
+    t.s0[i] = rule == kRuleSgd ? nullptr : slot0_h[i];
+    t.s1[i] = rule == kRuleSgd ? nullptr : slot1_h[i];
+  }
+  t.first_block[ntensors] = (int)blocks;
+  if (blocks == 0) return TFRS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (rule == kRuleSgd) return table_update_dense_launch(t, blocks, SgdRule{hyper_h[0]}, s);
+  if (rule == kRuleAdam) return table_update_dense_launch(t, blocks, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha}, s);
+  if (hyper_h[4] != 0.0f) return table_update_dense_launch(t, blocks, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]}, s);
+  return table_update_dense_launch(t, blocks, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]}, s);
+}
+
+extern "C" int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2,
+                              int advance, void *stream) {
+  TFRS_CHECK_ARG(step && alpha, "adam_tick: NULL pointer");
+  TFRS_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0, "adam_tick: 0 <= beta < 1");
+  TFRS_CHECK_ARG(advance == 0 || advance == 1, "adam_tick: advance must be 0 or 1");
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, alpha, learning_rate, beta_1,
+                     beta_2, advance);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}

@@ -24,9 +24,41 @@ runs the optimizer_v2 kernel ``ResourceApplyAdagradV2``, which divides by ``sqrt
 ``tests/test_ops_gpu.py`` cross-checks it against as an independent implementation;
 ``tools/tf_reference_vectors.py`` writes the TensorFlow-side vectors of both forms for a maintainer with
 TensorFlow installed (``tests/test_tf_vectors.py`` consumes them when present).
+
+``SGD``, ``Adam`` and ``Ftrl`` are the other three table optimizers the reference's embedding layer names
+(``layers/embedding/tpu_embedding_layer.py:37-49, 101-112``: ``'sgd'``, ``'adagrad'``, ``'adam'``, ``'ftrl'``).  They take
+the same ``(ids, rows)`` slices through one set of HIP kernels that is templated on the rule (``csrc/table_rules.h``;
+``tfrs_table_update_sparse`` on both routes of the Adagrad update, ``tfrs_table_update_dense_multi`` for dense
+parameters).  All arithmetic is float32 in the written operation order, without contraction; duplicate ids are summed
+first, in occurrence order from +0 -- the bits of the Adagrad path's sum, which on the sorted route cuts a run longer
+than a piece of max(32, 2^k >= d) positions at fixed positions into occurrence-order pieces and adds those in order;
+ids outside ``[0, vocab)`` are ignored.
+
+    SGD    ``w -= lr * g``                                               (``tf.keras.optimizers.SGD.update_step``,
+                                                                          momentum 0)
+    Adam   ``alpha = lr * sqrt(1 - beta_2^t) / (1 - beta_1^t)``          (``tf.keras.optimizers.Adam.update_step``;
+           ``m += (g - m) * (1 - beta_1)``                                ``t = iterations + 1``)
+           ``v += (g * g - v) * (1 - beta_2)``
+           ``w -= m * alpha / (sqrt(v) + epsilon)``
+    Ftrl   ``g' = g + 2 * shrink * w ;  n' = n + g * g``                 (``tf.keras.optimizers.Ftrl.update_step``,
+           ``lin += g' - (n'^p - n^p) / lr * w``                          ``p = -learning_rate_power``,
+           ``q = n'^p / lr + 2 * l2r``                                    ``l2r = l2 + beta / (2 lr)``)
+           ``w = (clip(lin, -l1, l1) - lin) / q ;  n = n'``
+
+On tables Adam is LAZY -- only looked-up rows have ``m``, ``v`` and ``w`` touched, a looked-up row whose summed gradient
+is exactly zero included: ``tf.tpu.experimental.embedding.Adam(lazy_adam=True)``, the table optimizer the reference's
+layer builds, and ``torch.optim.SparseAdam``; Keras's own Adam on ``IndexedSlices`` decays every row's moments.  ``t`` is
+one counter per optimizer, advanced once per ``step()``; it lives ON THE DEVICE (a host counter would be frozen by graph
+replay): the one-thread kernel ``tfrs_adam_tick`` increments it and writes ``alpha``, computed in float64 from the
+integer ``t`` and rounded once, into a device float the update kernels read.  Ftrl is row-sparse on tables as
+TensorFlow's ``ResourceSparseApplyFtrlV2`` is (untouched rows are not written; dense Keras Ftrl would re-solve them);
+``learning_rate_power`` is ``-0.5`` or ``0`` (a general ``powf`` has no error bound this project can state).  These
+numerics are reference-unpinned like Adagrad's: the reference's tests hold no vector for them, and the formulas are
+Keras's and TensorFlow's own; ``tools/tf_reference_vectors.py`` writes vectors for a maintainer with TensorFlow.
 """
 
-from typing import Iterable
+import ctypes
+from typing import Any, Dict, Iterable
 import weakref
 
 import torch
@@ -52,10 +84,11 @@ class SliceOwningOptimizer(torch.optim.Optimizer):
   (``Adagrad``, ``experimental.optimizers.ClippyAdagrad``): ownership of the tables' sparse-gradient mode
   (``_tfrs_sparse_grad`` / ``_tfrs_slices`` / ``_tfrs_sparse_owner``), ``close``, the per-parameter accumulator,
   ``reset_state_``, ``zero_grad`` and the version bumps after raw-pointer writes.  Subclasses pass their
-  hyper-parameters as ``defaults`` (``initial_accumulator_value`` among them) and implement ``step``."""
+  hyper-parameters as ``defaults`` (``initial_accumulator_value`` among them, for those that keep an accumulator) and
+  implement ``step``."""
 
   def __init__(self, params: Iterable, defaults: dict):
-    if defaults["initial_accumulator_value"] < 0.0:
+    if defaults.get("initial_accumulator_value", 0.0) < 0.0:
       raise ValueError("initial_accumulator_value must be non-negative")
     super().__init__(params, defaults)
     for group in self.param_groups:
@@ -185,3 +218,300 @@ class Adagrad(SliceOwningOptimizer):
       for lo in range(0, len(dense), 32):
         _adagrad_dense_multi(dense[lo:lo + 32], lr, eps, 2 if legacy else 1)
     return loss
+
+
+class _RuleOptimizer(SliceOwningOptimizer):
+  """What ``SGD``, ``Adam`` and ``Ftrl`` share: float32 parameters on the GPU go through the rule-templated kernels
+  (``tfrs_table_update_sparse`` for the slices of a table, ``tfrs_table_update_dense_multi`` for up to 32 dense tensors
+  per launch); a CPU tensor, a non-float32 or a non-contiguous parameter takes ``_formula`` in torch ops.  Every device
+  tensor a step mutates is a tensor inside ``self.state[p]``: the snapshot of a graph capture rolls the warm-up back."""
+
+  _RULE = -1        # the `rule` argument of the C entries
+  _SLOTS = ()       # state keys of the per-element slots, in kernel order
+  _CONFIG = ()
+
+  def get_config(self) -> Dict[str, Any]:
+    group = self.param_groups[0] if self.param_groups else self.defaults
+    return {k: group[k] for k in self._CONFIG}
+
+  @classmethod
+  def from_config(cls, params: Iterable, config: Dict[str, Any]):
+    return cls(params, **config)
+
+  # -- what a rule defines ---------------------------------------------------------------------------------------------
+  def _slot_init(self, group, key: str) -> float:
+    return 0.0
+
+  def _hyper(self, group):
+    """The ``hyper_h`` floats of the C entries (``csrc/table_rules.h``)."""
+    raise NotImplementedError
+
+  def _formula(self, w, slots, g, group, alpha):
+    """The module docstring's formula in torch ops, same operation order: ``(new w, [new slots])``."""
+    raise NotImplementedError
+
+  def _begin_step(self) -> None:
+    pass
+
+  def _alpha(self, group):
+    return None
+
+  # -- state -----------------------------------------------------------------------------------------------------------
+  def _slots_of(self, p, group):
+    state = self.state[p]
+    for key in self._SLOTS:
+      if key not in state:
+        state[key] = torch.full_like(p, self._slot_init(group, key), memory_format=torch.contiguous_format)
+    return [state[key] for key in self._SLOTS]
+
+  @torch.no_grad()
+  def reset_state_(self) -> None:
+    """Slots back to their initial value and Adam's counter to 0, in place (same storage)."""
+    for group in self.param_groups:
+      for p in group["params"]:
+        state = self.state[p] if p in self.state else {}
+        for key in self._SLOTS:
+          if key in state:
+            state[key].fill_(self._slot_init(group, key))
+        for key in ("step", "alpha"):
+          if key in state:
+            state[key].zero_()
+
+  def load_state_dict(self, state_dict) -> None:
+    super().load_state_dict(state_dict)
+    # (torch casts loaded state to the parameter's dtype, and leaves "step" wherever it was saved)
+    for p, state in self.state.items():
+      if "step" in state:
+        state["step"] = state["step"].to(device=p.device, dtype=torch.int64)
+      if "alpha" in state:
+        state["alpha"] = state["alpha"].to(device=p.device, dtype=torch.float32)
+
+  # -- the update ------------------------------------------------------------------------------------------------------
+  @staticmethod
+  def _on_kernel_route(p, slots, g) -> bool:
+    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
+            and p.is_contiguous() and all(s.is_contiguous() for s in slots) and g.device == p.device)
+
+  @staticmethod
+  def _wrote(*tensors) -> None:      # (written through raw pointers)
+    for t in tensors:
+      torch.autograd.graph.increment_version(t)
+
+  def _sparse_call(self, p, slots, ids, rows, hyper, alpha) -> None:
+    from recommenders_amd import _lib
+    lib = _lib.load()
+    d = p.shape[1]
+    if ids.dtype not in (torch.int32, torch.int64):
+      ids = ids.long()
+    flat = ids.reshape(-1).contiguous()
+    n = flat.numel()
+    g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
+    rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
+    ws = torch.empty((lib.tfrs_table_update_workspace_bytes(n, rowscan),), dtype=torch.uint8, device=p.device)
+    s0, s1 = (list(slots) + [None, None])[:2]
+    _lib.check(lib.tfrs_table_update_sparse(
+        self._RULE, hyper, _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d,
+        p.shape[0], _lib.ptr(p.data), _lib.ptr(s0), _lib.ptr(s1), rowscan, _lib.ptr(ws), ws.numel(),
+        _lib.current_stream()))
+    self._wrote(p, *slots)
+
+  def _sparse_fallback(self, p, slots, ids, rows, group, alpha) -> None:
+    d = p.shape[1]
+    flat = ids.reshape(-1).long()
+    g = rows.reshape(flat.numel(), d)
+    keep = (flat >= 0) & (flat < p.shape[0])
+    flat, g = flat[keep], g[keep]
+    uniq, inverse = torch.unique(flat, return_inverse=True)
+    # duplicates summed first, in the gradient's own precision like the kernels (on the CPU index_add_ adds in
+    # occurrence order)
+    summed = torch.zeros((uniq.numel(), d), dtype=g.dtype, device=g.device).index_add_(0, inverse, g)
+    w, new = self._formula(p.data[uniq], [s[uniq] for s in slots], summed.to(p.dtype), group, alpha)
+    p.data[uniq] = w
+    for s, value in zip(slots, new):
+      s[uniq] = value
+
+  def _dense_call(self, items, hyper, alpha) -> None:
+    from recommenders_amd import _lib
+    n = len(items)
+    vp, i64a = ctypes.c_void_p * n, ctypes.c_int64 * n
+    slot = lambda k: vp(*[s[k].data_ptr() for _, s, _ in items]) if len(self._SLOTS) > k else None
+    _lib.check(_lib.load().tfrs_table_update_dense_multi(
+        self._RULE, hyper, _lib.ptr(alpha), n, vp(*[p.data_ptr() for p, _, _ in items]), slot(0), slot(1),
+        vp(*[g.data_ptr() for _, _, g in items]), i64a(*[p.numel() for p, _, _ in items]), _lib.current_stream()))
+    for p, slots, _ in items:
+      self._wrote(p, *slots)
+
+  @torch.no_grad()
+  def step(self, closure=None):
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    self._begin_step()
+    for group in self.param_groups:
+      hyper = (ctypes.c_float * 8)(*self._hyper(group))
+      alpha = self._alpha(group)
+      dense = []      # (parameter, slots, gradient) of every dense parameter of the group on the kernel route
+      for p in group["params"]:
+        slots = self._slots_of(p, group)
+        merged = self._merged_slices(p)
+        if merged is not None:
+          ids, rows = merged
+          if self._on_kernel_route(p, slots, rows) and ids.device == p.device:
+            self._sparse_call(p, slots, ids, rows, hyper, alpha)
+          else:
+            self._sparse_fallback(p, slots, ids.to(p.device), rows.to(p.device), group, alpha)
+        if p.grad is None:
+          continue
+        g = p.grad
+        if self._on_kernel_route(p, slots, g):
+          dense.append((p, slots, g.contiguous()))
+          continue
+        w, new = self._formula(p.data, slots, (g.to_dense() if g.is_sparse else g).to(p.dtype), group, alpha)
+        p.data.copy_(w)
+        for s, value in zip(slots, new):
+          s.copy_(value)
+      for lo in range(0, len(dense), 32):
+        self._dense_call(dense[lo:lo + 32], hyper, alpha)
+    return loss
+
+
+class SGD(_RuleOptimizer):
+  """``tf.keras.optimizers.SGD(learning_rate)`` without momentum: ``w -= lr * g``."""
+
+  _RULE = 0
+  _CONFIG = ("learning_rate",)
+
+  def __init__(self, params: Iterable, learning_rate: float = 0.01, momentum: float = 0.0, nesterov: bool = False):
+    if momentum != 0.0 or nesterov:
+      raise NotImplementedError("SGD: momentum and nesterov are not implemented")
+    super().__init__(params, dict(learning_rate=float(learning_rate)))
+
+  def _hyper(self, group):
+    return [group["learning_rate"]]
+
+  def _formula(self, w, slots, g, group, alpha):
+    return w - group["learning_rate"] * g, []
+
+
+class Adam(_RuleOptimizer):
+  """``tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon)``; lazy on tables (module docstring).  The step
+  counter ``state[first parameter]["step"]`` (int64) and each group's ``alpha`` live on the device."""
+
+  _RULE = 1
+  _SLOTS = ("m", "v")
+  _CONFIG = ("learning_rate", "beta_1", "beta_2", "epsilon")
+
+  def __init__(self, params: Iterable, learning_rate: float = 0.001, beta_1: float = 0.9, beta_2: float = 0.999,
+               epsilon: float = 1e-7):
+    if not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0:
+      raise ValueError("Adam: beta_1 and beta_2 must be in [0, 1)")
+    if epsilon < 0.0:
+      raise ValueError("Adam: epsilon must be non-negative")
+    super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
+                                  epsilon=float(epsilon)))
+    if len({p.device for group in self.param_groups for p in group["params"]}) > 1:
+      self.close()
+      raise ValueError("Adam: all parameters must live on one device (the step counter is one device tensor that the "
+                       "kernels read); build one Adam per device")
+
+  @property
+  def iterations(self) -> torch.Tensor:
+    """The device counter ``t`` (steps taken so far; 0-d int64)."""
+    return self._counter()
+
+  def _counter(self) -> torch.Tensor:
+    first = self.param_groups[0]["params"][0]
+    state = self.state[first]
+    if "step" not in state:
+      state["step"] = torch.zeros((), dtype=torch.int64, device=first.device)
+    return state["step"]
+
+  def _alpha(self, group) -> torch.Tensor:
+    first = group["params"][0]
+    state = self.state[first]
+    if "alpha" not in state:
+      state["alpha"] = torch.zeros((), dtype=torch.float32, device=first.device)
+    return state["alpha"]
+
+  def _begin_step(self) -> None:
+    step = self._counter()
+    for i, group in enumerate(self.param_groups):
+      alpha = self._alpha(group)
+      lr, b1, b2 = group["learning_rate"], group["beta_1"], group["beta_2"]
+      if step.is_cuda:
+        from recommenders_amd import _lib
+        _lib.check(_lib.load().tfrs_adam_tick(_lib.ptr(step), _lib.ptr(alpha), lr, b1, b2, 1 if i == 0 else 0,
+                                              _lib.current_stream()))
+        self._wrote(step, alpha)
+      else:
+        if i == 0:
+          step.add_(1)
+        t = int(step)
+        alpha.fill_(lr * (1.0 - b2 ** t) ** 0.5 / (1.0 - b1 ** t))
+
+  def _hyper(self, group):
+    return [1.0 - group["beta_1"], 1.0 - group["beta_2"], group["epsilon"]]
+
+  def _formula(self, w, slots, g, group, alpha):
+    m, v = slots
+    m = m + (g - m) * (1.0 - group["beta_1"])
+    v = v + (g * g - v) * (1.0 - group["beta_2"])
+    return w - m * alpha.to(w.dtype) / (torch.sqrt(v) + group["epsilon"]), [m, v]
+
+
+class Ftrl(_RuleOptimizer):
+  """``tf.keras.optimizers.Ftrl``; row-sparse on tables; ``learning_rate_power`` is ``-0.5`` or ``0`` (module
+  docstring)."""
+
+  _RULE = 2
+  _SLOTS = ("accumulator", "linear")
+  _CONFIG = ("learning_rate", "learning_rate_power", "initial_accumulator_value", "l1_regularization_strength",
+             "l2_regularization_strength", "l2_shrinkage_regularization_strength", "beta")
+
+  def __init__(self, params: Iterable, learning_rate: float = 0.001, learning_rate_power: float = -0.5,
+               initial_accumulator_value: float = 0.1, l1_regularization_strength: float = 0.0,
+               l2_regularization_strength: float = 0.0, l2_shrinkage_regularization_strength: float = 0.0,
+               beta: float = 0.0):
+    if initial_accumulator_value < 0.0:
+      raise ValueError("`initial_accumulator_value` needs to be positive or zero. Received: "
+                       f"initial_accumulator_value={initial_accumulator_value}.")
+    if learning_rate_power > 0.0:
+      raise ValueError(f"`learning_rate_power` needs to be negative or zero. Received: "
+                       f"learning_rate_power={learning_rate_power}.")
+    for name, value in (("l1_regularization_strength", l1_regularization_strength),
+                        ("l2_regularization_strength", l2_regularization_strength),
+                        ("l2_shrinkage_regularization_strength", l2_shrinkage_regularization_strength),
+                        ("beta", beta)):
+      if value < 0.0:
+        raise ValueError(f"`{name}` needs to be positive or zero. Received: {name}={value}.")
+    if learning_rate <= 0.0:
+      raise ValueError("Ftrl: learning_rate must be positive (the update divides by it)")
+    if learning_rate_power not in (-0.5, 0.0):
+      raise NotImplementedError("Ftrl: learning_rate_power must be -0.5 or 0 (a general powf has no error bound this "
+                                "project can state)")
+    super().__init__(params, dict(
+        learning_rate=float(learning_rate), learning_rate_power=float(learning_rate_power),
+        initial_accumulator_value=float(initial_accumulator_value),
+        l1_regularization_strength=float(l1_regularization_strength),
+        l2_regularization_strength=float(l2_regularization_strength),
+        l2_shrinkage_regularization_strength=float(l2_shrinkage_regularization_strength), beta=float(beta)))
+
+  def _slot_init(self, group, key: str) -> float:
+    return group["initial_accumulator_value"] if key == "accumulator" else 0.0
+
+  def _hyper(self, group):
+    lr = group["learning_rate"]
+    l2r = group["l2_regularization_strength"] + group["beta"] / (2.0 * lr)
+    return [lr, group["l1_regularization_strength"], 2.0 * l2r, 2.0 * group["l2_shrinkage_regularization_strength"],
+            group["learning_rate_power"]]
+
+  def _formula(self, w, slots, g, group, alpha):
+    n, lin = slots
+    lr, l1, two_l2r, two_shrink, power = self._hyper(group)
+    gp = g + two_shrink * w
+    n2 = n + g * g
+    pn2, pn = (torch.sqrt(n2), torch.sqrt(n)) if power != 0.0 else (torch.ones_like(n2), torch.ones_like(n))
+    lin = lin + (gp - (pn2 - pn) / lr * w)
+    q = pn2 / lr + two_l2r
+    return (torch.clamp(lin, -l1, l1) - lin) / q, [n2, lin]

@@ -7,7 +7,8 @@ the hand-over: a maintainer with TensorFlow runs
     pip install tensorflow tf-keras        # TF >= 2.16 needs tf-keras and TF_USE_LEGACY_KERAS=1, as the reference's
     TF_USE_LEGACY_KERAS=1 python tools/tf_reference_vectors.py      # tools/build_scripts/pip_install.sh does
 
-and commits the three files it writes under tests/golden/ (tf_combiners.json, tf_adagrad.json, tf_train_step.json).
+and commits the files it writes under tests/golden/ (tf_combiners.json, tf_adagrad.json, tf_train_step.json, and
+tf_table_optimizers.json, which no test consumes yet).
 `pytest tests/test_tf_vectors.py` then holds the oracle (CPU) and the HIP kernels (GPU) to TensorFlow's own numbers,
 and the "parity unpinned" notes of oracle/embedding.py, DESIGN.md section 2 and INTEGRATION.md can be dropped.  The
 inputs are generated HERE from fixed seeds with NumPy only and stored in the files: the tests never need TensorFlow.
@@ -20,6 +21,8 @@ What is recorded, and the reference code it pins:
                repeats ids (README.md:84 under models/base.py:77-78), for the optimizer class the installed TF gives
                (`formula`: "sqrt(acc+eps)" for the TF >= 2.11 / tf-keras optimizer, "sqrt(acc)+eps" for optimizer_v2),
                and, where available, for tf.keras.optimizers.legacy.Adagrad as well;
+  * sgd / adam / ftrl  three steps of the Keras optimizers on the same table with the dense form of the same gradients, and
+               Ftrl's row-sparse kernel ResourceSparseApplyFtrlV2 (recommenders_amd.optimizers.SGD / Adam / Ftrl);
   * train step one tfrs-style two-tower step WITHOUT tensorflow_recommenders installed: embeddings -> in-batch
                softmax (tasks/retrieval.py:172-210 restated with tf ops: eye labels, CategoricalCrossentropy(from_logits,
                SUM)) -> tape.gradient -> Adagrad.apply_gradients; records loss, both tables and accumulators after
@@ -124,6 +127,55 @@ def main() -> None:
   with open(os.path.join(OUT, "tf_adagrad.json"), "w") as f:
     json.dump({"meta": meta, **ada}, f)
 
+  # ---- SGD / Adam / Ftrl (recommenders_amd.optimizers; layers/embedding/tpu_embedding_layer.py:37-49 names them as table
+  # optimizers).  "dense": three apply_gradients steps of the Keras class on a dense variable with the DENSE form of the
+  # gradient (duplicates summed in float32 in occurrence order, untouched rows zero) -- pins the formulas; the rows that
+  # were looked up are what the lazy / row-sparse table updates of this project must reproduce while their moments have
+  # only ever been touched together (step 1 for Adam; every step for SGD).  "sparse_ftrl": the same steps through
+  # tf.raw_ops.ResourceSparseApplyFtrlV2 on the unique ids -- the row-sparse form itself.  TensorFlow has no lazy Adam
+  # in core (tf.tpu.experimental.embedding.Adam(lazy_adam=True) runs on TPU only): lazy Adam stays pinned by
+  # torch.optim.SparseAdam (tests/test_table_optimizers_host.py).
+  def dense_gradient(ids_t, grads_t):
+    out = np.zeros(table0.shape, np.float32)
+    for i, g in zip(ids_t, grads_t):          # occurrence order, float32
+      out[i] += g
+    return out
+
+  configs = {"sgd": (tf.keras.optimizers.SGD, dict(learning_rate=0.5)),
+             "adam": (tf.keras.optimizers.Adam, dict(learning_rate=0.01, beta_1=0.9, beta_2=0.999, epsilon=1e-7)),
+             "ftrl": (tf.keras.optimizers.Ftrl, dict(learning_rate=0.1, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+                                                     l1_regularization_strength=0.01, l2_regularization_strength=0.02,
+                                                     l2_shrinkage_regularization_strength=0.003, beta=0.1))}
+  rec = {"table": _l(table0), "steps": [{"ids": _l(i), "grads": _l(g), "dense": _l(dense_gradient(i, g))} for i, g in steps],
+         "optimizers": {}}
+  for name, (cls, kwargs) in configs.items():
+    var = tf.Variable(table0)
+    opt = cls(**kwargs)
+    tables = []
+    for ids_t, grads_t in steps:
+      opt.apply_gradients([(tf.constant(dense_gradient(ids_t, grads_t)), var)])
+      tables.append(_l(var.numpy()))
+    rec["optimizers"][name] = {"class": cls.__module__ + "." + cls.__name__, "config": kwargs, "dense": tables}
+  try:
+    kw = configs["ftrl"][1]
+    var, accum, linear = tf.Variable(table0), tf.Variable(np.full_like(table0, 0.1)), tf.Variable(np.zeros_like(table0))
+    tables = []
+    for ids_t, grads_t in steps:
+      dense = dense_gradient(ids_t, grads_t)
+      uniq = np.unique(ids_t)
+      tf.raw_ops.ResourceSparseApplyFtrlV2(
+          var=var.handle, accum=accum.handle, linear=linear.handle, grad=tf.constant(dense[uniq]), indices=tf.constant(uniq),
+          lr=tf.constant(np.float32(kw["learning_rate"])), l1=tf.constant(np.float32(kw["l1_regularization_strength"])),
+          l2=tf.constant(np.float32(kw["l2_regularization_strength"] + kw["beta"] / (2.0 * kw["learning_rate"]))),
+          l2_shrinkage=tf.constant(np.float32(kw["l2_shrinkage_regularization_strength"])),
+          lr_power=tf.constant(np.float32(kw["learning_rate_power"])))
+      tables.append({"table": _l(var.numpy()), "accumulator": _l(accum.numpy()), "linear": _l(linear.numpy())})
+    rec["optimizers"]["ftrl"]["sparse_ftrl"] = tables
+  except Exception as e:     # noqa: BLE001 -- the dense vectors above stand on their own
+    rec["optimizers"]["ftrl"]["sparse_ftrl_error"] = repr(e)
+  with open(os.path.join(OUT, "tf_table_optimizers.json"), "w") as f:
+    json.dump({"meta": meta, **rec}, f)
+
   # ---- one two-tower train step, three times
   users0, items0, batches = train_step_inputs()
   u, v = tf.Variable(users0), tf.Variable(items0)
@@ -151,7 +203,7 @@ def main() -> None:
                          "items": _l(v.numpy())})
   with open(os.path.join(OUT, "tf_train_step.json"), "w") as f:
     json.dump({"meta": meta, **rec}, f)
-  print("wrote tf_combiners.json, tf_adagrad.json, tf_train_step.json under", OUT)
+  print("wrote tf_combiners.json, tf_adagrad.json, tf_table_optimizers.json, tf_train_step.json under", OUT)
 
 
 if __name__ == "__main__":
