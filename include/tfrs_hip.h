@@ -368,6 +368,10 @@ int tfrs_embedding_scatter_add_bwd(const float *grad_out, const int64_t *sorted_
  * scatter-add / fused Adagrad.  ids outside [0, vocab) are ignored -- they can never write
  * outside the table.  workspace from tfrs_embedding_scatter_add_workspace_bytes(n). */
 size_t tfrs_embedding_scatter_add_workspace_bytes(int64_t n);
+/* The plan of that sort for a vocabulary (host only, no device call): *passes LSD passes of *digit_bits (8, 9 or 10)
+ * bits each -- the smallest pass count that covers the bits of vocab plus the one bit that sets the invalid key apart,
+ * at the narrowest digit that reaches it.  The sort launches exactly this plan. */
+int tfrs_embedding_sort_plan(int64_t vocab, int *passes, int *digit_bits);
 int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const void *ids, int ids_are_i64,
                                         int64_t n, int d, int64_t vocab,
                                         float *grad_table_or_table, float *accum, float lr,

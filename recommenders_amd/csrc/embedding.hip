@@ -987,6 +987,28 @@ extern "C" size_t tfrs_embedding_scatter_add_workspace_bytes(int64_t n) {
          tfrs::sort_al((tiles * 4 / tfrs::kScanChunk + 1) * 1024 * 4);
 }
 
+// The sort's plan for a vocabulary: `passes` LSD passes of `digit_bits` (8, 9 or 10) bits each.  sort_id_positions
+// launches exactly this plan (the exported function is the only place that computes it).
+extern "C" int tfrs_embedding_sort_plan(int64_t vocab, int *passes_out, int *digit_bits_out) {
+  TFRS_CHECK_ARG(vocab >= 1 && passes_out && digit_bits_out, "embedding_sort_plan: bad argument");
+  // digits that can differ: the bits of vocab (0xFFFFFFFF of invalid ids needs the top pass too,
+  // which the last valid pass provides as long as it covers a bit above vocab - 1)
+  int bits = 1;
+  while (bits < 32 && (1ll << bits) <= vocab) ++bits;   // 2^bits > vocab: invalid keys have bit `bits`.. set
+  int passes = (bits + 1 + 7) / 8;
+  if (passes > 4) passes = 4;
+  // 9 or 10 bits per pass where that saves a whole pass (26 significant bits: 3 x 9; 28 .. 30: 3 x 10)
+  int digit_bits = 8;
+  for (int b = 9; b <= 10; ++b)
+    if ((bits + 1 + b - 1) / b < passes) {
+      passes = (bits + 1 + b - 1) / b;
+      digit_bits = b;
+    }
+  *passes_out = passes;
+  *digit_bits_out = digit_bits;
+  return TFRS_OK;
+}
+
 // The sort alone: (id, position) pairs of `ids` in `workspace` (tfrs_embedding_scatter_add_workspace_bytes(n)), stable,
 // ids outside [0, vocab) last.  Returns the index `cur` of the sorted buffers: sorted ids = keys[cur], positions =
 // vals[cur]; keys[cur ^ 1] (n uint32) is free.  Shared by the scatter-add / Adagrad update and ClippyAdagrad's two passes.
@@ -1004,19 +1026,8 @@ static int sort_id_positions(const void *ids, int ids_are_i64, int64_t n, int64_
   const int64_t nseg = tiles * 4, nchunk = (nseg + kScanChunk - 1) / kScanChunk;
   hipLaunchKernelGGL(sort_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, ids_are_i64, n,
                      vocab, keys[0], vals[0]);
-  // digits that can differ: the bits of vocab (0xFFFFFFFF of invalid ids needs the top pass too,
-  // which the last valid pass provides as long as it covers a bit above vocab - 1)
-  int bits = 1;
-  while (bits < 32 && (1ll << bits) <= vocab) ++bits;   // 2^bits > vocab: invalid keys have bit `bits`.. set
-  int passes = (bits + 1 + 7) / 8;
-  if (passes > 4) passes = 4;
-  // 9 or 10 bits per pass where that saves a whole pass (26 significant bits: 3 x 9; 28 .. 30: 3 x 10)
-  int digit_bits = 8;
-  for (int b = 9; b <= 10; ++b)
-    if ((bits + 1 + b - 1) / b < passes) {
-      passes = (bits + 1 + b - 1) / b;
-      digit_bits = b;
-    }
+  int passes = 0, digit_bits = 8;   // (a refused vocab -- every caller checks vocab >= 1 first -- sorts nothing)
+  (void)tfrs_embedding_sort_plan(vocab, &passes, &digit_bits);
   int cur = 0;
   auto one_pass = [&](auto bc, int p) {
     constexpr int B = decltype(bc)::value;
