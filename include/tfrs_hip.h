@@ -528,6 +528,42 @@ int tfrs_inbatch_softmax_ce_bwd(const float *q, const float *c, int64_t nq, int6
                                 void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The same loss for MULTI-HEAD (max-sim) queries q[nq, heads, d] (tasks/retrieval.py:172-176), without the
+ * [nq * heads, nc] head scores or the [nq, nc] logits:
+ *   M_bc  = max_h (q_bh . c_c)              the max is taken on the raw dot products, as the reference does
+ *   S_bc  = M_bc [/ temperature] [- log clip(p_c)] [+ MIN_FLOAT accidental hits] [MIN_FLOAT where !mask]
+ *   loss  = sum_b w_b (logsumexp_c S_bc - S_bb)
+ *   G_bc  = gloss * w_b * (exp(S_bc - lse_b) - [b == c]) / temperature      (0 where masked)
+ *   h*(b,c) = the LOWEST head index attaining the max (the first-index rule of an argmax; TensorFlow's reduce_max
+ *             splits the gradient evenly among tied heads -- a deviation at exact ties only)
+ *   dq_bh = sum_c [h == h*(b,c)] G_bc c_c ,   dc_c = sum_b G_bc q_{b,h*(b,c)}
+ * 1 <= heads <= 32, 1 <= d <= TFRS_MAX_DIM, nc >= nq; anything else is TFRS_EINVAL before the device is touched,
+ * as are NULL pointers and a workspace below tfrs_inbatch_softmax_mh_workspace_bytes (shared by both calls).
+ * score_mask is [nq, nc]; out_lse[nq], out_pos[nq] are kept for the backward; dq is [nq, heads, d], dc [nc, d].
+ * f32 MFMA arithmetic throughout; deterministic (no float atomics).
+ * ------------------------------------------------------------------------- */
+size_t tfrs_inbatch_softmax_mh_workspace_bytes(int64_t nq, int heads, int64_t nc, int d);
+int tfrs_inbatch_softmax_mh_ce_fwd(const float *q, const float *c, int64_t nq, int heads, int64_t nc, int d,
+                                   const float *sample_weight, float inv_temperature,
+                                   const float *log_q_correction, const int64_t *cand_ids,
+                                   const uint8_t *score_mask, float *out_loss, float *out_lse, float *out_pos,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int tfrs_inbatch_softmax_mh_ce_bwd(const float *q, const float *c, int64_t nq, int heads, int64_t nc, int d,
+                                   const float *sample_weight, float inv_temperature,
+                                   const float *log_q_correction, const int64_t *cand_ids,
+                                   const uint8_t *score_mask, const float *lse, const float *gloss, float *dq,
+                                   float *dc, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Multi-head exact top-K (BruteForce on queries [nq, heads, d]): scores / rows [nq, heads, k_in] are the top-k_in
+ * lists of the nq * heads flat (query, head) rows (descending; row < 0 = empty).  Writes, per query, the top-k_out
+ * of max_h score under (score descending, row ascending): a row that appears in several lists counts once, with
+ * its highest score.  With k_out <= k_in that is the exact top-k_out of the max over heads (the union of the lists
+ * contains it).  heads <= 32, k_in <= TFRS_MAX_K, heads * k_in <= 8192 (one workgroup's LDS); empty output
+ * slots carry row -1 and score -inf. */
+int tfrs_topk_merge_heads(const float *scores, const int32_t *rows, int64_t nq, int heads, int k_in, int k_out,
+                          float *out_scores, int32_t *out_rows, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Keras CategoricalCrossentropy(from_logits=True, reduction=SUM) on an EXPLICIT logits matrix
  * (tasks/retrieval.py:86-87, :210) -- only for the Retrieval paths that must build [nq, nc] (multi-head queries
  * :172-176, dims above TFRS_MAX_DIM, batch metrics / hard negatives after a logit adjustment :205-208); the default

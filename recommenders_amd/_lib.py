@@ -104,6 +104,12 @@ SIGNATURES = {
                                             P, P, P, P, c_size_t, P]),
     "tfrs_inbatch_softmax_ce_bwd": (c_int, [P, P, c_i64, c_i64, c_int, P, c_float, P, P, P,
                                             P, P, P, P, P, c_size_t, c_int, P]),
+    "tfrs_inbatch_softmax_mh_workspace_bytes": (c_size_t, [c_i64, c_int, c_i64, c_int]),
+    "tfrs_inbatch_softmax_mh_ce_fwd": (c_int, [P, P, c_i64, c_int, c_i64, c_int, P, c_float, P, P, P,
+                                               P, P, P, P, c_size_t, P]),
+    "tfrs_inbatch_softmax_mh_ce_bwd": (c_int, [P, P, c_i64, c_int, c_i64, c_int, P, c_float, P, P, P,
+                                               P, P, P, P, P, c_size_t, P]),
+    "tfrs_topk_merge_heads": (c_int, [P, P, c_i64, c_int, c_int, c_int, P, P, P]),
     "tfrs_logits_ce_fwd": (c_int, [P, P, c_i64, c_i64, P, P, P, P, P]),
     "tfrs_logits_ce_bwd": (c_int, [P, P, c_i64, c_i64, P, P, P, P, P, P]),
     "tfrs_cross_fwd": (c_int, [P, P, P, P, c_float, c_i64, c_int, P, P]),

@@ -29,6 +29,7 @@ SOURCES = [
     "topk_select16.hip",
     "topk_raw.hip",
     "topk_api.hip",
+    "topk_merge_heads.hip",
     "metric_fused.hip",
     "dedup.hip",
     "embedding.hip",
@@ -38,6 +39,7 @@ SOURCES = [
     "hashing.hip",
     "softmax.hip",
     "softmax16.hip",
+    "softmax_mh.hip",
     "logits_ce.hip",
     "interaction.hip",
     "gemm16.hip",

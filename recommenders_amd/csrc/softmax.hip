@@ -29,44 +29,9 @@
 
 #include <stdlib.h>
 
-#include "mfma_tile.h"
+#include "softmax_args.h"
 
 namespace tfrs {
-
-constexpr float kMinFloat = -3.4028234663852886e36f;  // np.finfo(float32).min / 100
-
-struct SoftmaxArgs {
-  const float *q, *c;
-  int64_t nq, nc;
-  int d;
-  const float *w;       // [nq] sample weights or NULL
-  float inv_t;          // 1 / temperature
-  const float *corr;    // [nc] log(clip(p, 1e-6, 1)) or NULL
-  const int64_t *ids;   // [nc] candidate ids (accidental-hit removal) or NULL
-  const uint8_t *mask;  // [nq, nc] score_mask or NULL
-  int nsplit;
-  int64_t split_len;    // multiple of 32
-  float *pm, *pl;       // [nsplit, nq] partial max / sum-exp
-  float *ppos;          // [nq] positive logit
-  const float *lse;     // [nq]
-  const float *gloss;   // device scalar or NULL (= 1)
-  float *partial;       // [nsplit, rows, d] partial gradients
-  uint32_t *ticket;     // finalize kernel's arrival counter (re-armed by the forward kernel)
-};
-
-__device__ __forceinline__ float make_logit(float dot, int64_t query, int64_t cand,
-                                            const SoftmaxArgs &a, float corr_c,
-                                            int64_t id_q, int64_t id_c, bool *masked) {
-  float v = dot * a.inv_t;
-  if (a.corr) v -= corr_c;
-  if (a.ids && cand != query && id_c == id_q) v += kMinFloat;
-  *masked = false;
-  if (a.mask && !a.mask[query * a.nc + cand]) {
-    v = kMinFloat;
-    *masked = true;
-  }
-  return v;
-}
 
 // PLAIN: no sampling-probability correction, no accidental-hit removal, no score mask (the
 // default Retrieval configuration): those branches are compiled out of the tile epilogue.
@@ -342,9 +307,7 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const float *parti
   }
 }
 
-static void plan(int64_t n_rows, int64_t n_stream, int *nsplit, int64_t *split_len) {
-  const int64_t row_blocks = (n_rows + 31) / 32;
-  const int64_t tiles = (n_stream + 31) / 32;
+void softmax_plan_blocks(int64_t row_blocks, int64_t tiles, int *nsplit, int64_t *split_len) {
   static const int64_t target_waves = [] {
     const char *v = option("TFRS_SOFTMAX_WAVES");
     return (v && *v) ? (int64_t)atoll(v) : (int64_t)2048;  // ~2 waves per SIMD on 256 CUs
@@ -355,6 +318,21 @@ static void plan(int64_t n_rows, int64_t n_stream, int *nsplit, int64_t *split_l
   const int64_t per = (tiles + want - 1) / want;
   *split_len = per * 32;
   *nsplit = (int)((tiles + per - 1) / per);
+}
+
+static void plan(int64_t n_rows, int64_t n_stream, int *nsplit, int64_t *split_len) {
+  softmax_plan_blocks((n_rows + 31) / 32, (n_stream + 31) / 32, nsplit, split_len);
+}
+
+void softmax_launch_finalize(const SoftmaxArgs &a, float *out_loss, float *out_lse, float *out_pos,
+                             double *block_part, hipStream_t s) {
+  hipLaunchKernelGGL(softmax_finalize_kernel, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, s, a, out_loss,
+                     out_lse, out_pos, block_part, a.ticket);
+}
+
+void softmax_launch_reduce(const float *partial, int nsplit, int64_t count, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 2048)), dim3(256),
+                     0, s, partial, nsplit, count, out);
 }
 
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }

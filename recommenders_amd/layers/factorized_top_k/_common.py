@@ -43,6 +43,15 @@ def _as_f32_matrix(x: ArrayLike, what: str) -> Tensor:
   return x.to(device=_device(), dtype=torch.float32).contiguous()
 
 
+def _as_f32_queries(x: ArrayLike) -> Tensor:
+  """Float32, contiguous, on the GPU: ``[B, D]`` queries or multi-head ``[B, H, D]`` queries (``BruteForce``)."""
+  if not isinstance(x, torch.Tensor):
+    x = torch.as_tensor(np.asarray(x))
+  if x.dim() == 3:
+    return x.to(device=_device(), dtype=torch.float32).contiguous()
+  return _as_f32_matrix(x, "queries")
+
+
 def _workspace(nbytes: int) -> Tensor:
   return torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=_device())
 
@@ -51,6 +60,8 @@ _RAW_DIMS = (8, 16, 32, 64, 128)   # dims whose row-major rows the grouped Strea
 _RAW_MAX_BLOCKS = 192              # blocks per tfrs_streaming_topk_update_blocks call (kRawMaxBlocks)
 MAX_FUSED_DIM = 128    # TFRS_MAX_DIM: embedding dims the fused scan kernels keep in registers
 MAX_FUSED_K = 1024     # TFRS_MAX_K: results per query the selection kernels hold in one pass
+MAX_MERGE_HEADS = 32   # heads of a multi-head query (BruteForce on [B, H, D] queries)
+MAX_MERGE_PAIRS = 8192  # heads * k (score, row) pairs one workgroup of tfrs_topk_merge_heads holds in LDS
 _WIDE_BLOCK = 32768    # candidate rows per materialised score block on the wide-dim path
 
 _INT32_MAX = 0x7FFFFFFF

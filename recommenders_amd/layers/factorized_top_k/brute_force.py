@@ -9,9 +9,9 @@ import torch
 from recommenders_amd import _lib
 
 from ._base import TopK
-from ._common import (MAX_FUSED_DIM, MAX_FUSED_K, NOT_INDEXED_MESSAGE, ArrayLike, Tensor, _as_f32_matrix,
-                      _check_candidates_with_identifiers, _check_k_against_rows, _check_query_dim, _device,
-                      _host_identifiers, _Identifiers, _IndexHandle, _iter_blocks, _save_npz,
+from ._common import (MAX_FUSED_DIM, MAX_FUSED_K, MAX_MERGE_HEADS, MAX_MERGE_PAIRS, NOT_INDEXED_MESSAGE, ArrayLike,
+                      Tensor, _as_f32_matrix, _as_f32_queries, _check_candidates_with_identifiers,
+                      _check_k_against_rows, _check_query_dim, _device, _host_identifiers, _Identifiers, _IndexHandle, _iter_blocks, _save_npz,
                       _validate_candidates, _wide_topk_update, _workspace)
 
 
@@ -107,6 +107,13 @@ class BruteForce(TopK):
   ``index`` copies the candidates into a layer-owned, MFMA-friendly packed corpus in
   HBM (:559-584); ``call`` is one fused scan, the ``[B, N]`` score matrix is never
   materialised.
+
+  Multi-head queries ``[B, H, D]`` (the max-sim queries of ``tasks.Retrieval``, tasks/retrieval.py:172-176; not in
+  the reference's layer, which scores 2-D queries only): the score of a candidate is the max over the query's heads
+  and the result is the exact top-k of that score under (score descending, row ascending).  The ``B * H`` flat rows
+  are searched with the same ``k`` and ``tfrs_topk_merge_heads`` merges each query's ``H`` lists (the union of the
+  per-head top-k lists contains the top-k of the max; csrc/topk_merge_heads.hip).  Envelope: ``H <= 32``,
+  ``k <= 1024``, ``H * k <= 8192``, ``D <= 128``.  Rank-2 input keeps meaning a batch of single-head queries.
 
   ``dedup`` (default ``"auto"``; not in the reference): ``tf.math.top_k`` breaks ties by the lower
   index (:605), so on a corpus with many EXACT copies of a row (default / cold-start embeddings,
@@ -228,9 +235,41 @@ class BruteForce(TopK):
                               ids=_Identifiers(np.concatenate(ids, axis=0) if ids else None, n))
     return self
 
+  def _embed(self, queries) -> Tensor:
+    if self.query_model is not None:
+      queries = self.query_model(queries)
+    return _as_f32_queries(queries)
+
+  def _query_rows_heads(self, q: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """Multi-head queries ``[B, H, D]``: top-k of ``max_h q_bh . c`` -- the flat rows' top-k lists, merged per query."""
+    st = self._state
+    nq, heads, d = q.shape
+    if d != st.d:
+      raise ValueError(f"Query dimension {d} does not match the index ({st.d}).")
+    _check_k_against_rows(k, st.n)
+    if not 1 <= heads <= MAX_MERGE_HEADS:
+      raise ValueError(f"BruteForce: multi-head queries take 1 to {MAX_MERGE_HEADS} heads (got {heads}).")
+    if st.wide is not None:
+      raise ValueError(f"BruteForce: multi-head queries need an embedding dim of at most {MAX_FUSED_DIM} (index: {d}).")
+    if k > MAX_FUSED_K:
+      raise ValueError(f"BruteForce: multi-head queries take k <= {MAX_FUSED_K} (got k={k}).")
+    if heads * k > MAX_MERGE_PAIRS:
+      raise ValueError(f"BruteForce: heads * k = {heads * k} is above the {MAX_MERGE_PAIRS} (score, row) pairs the "
+                       f"multi-head merge holds per query.")
+    scores, rows = self._query_rows(q.reshape(nq * heads, d), k, embedded=True)
+    if heads == 1:
+      return scores, rows
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    out_r = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    _lib.check(_lib.load().tfrs_topk_merge_heads(_lib.ptr(scores), _lib.ptr(rows), nq, heads, k, k,
+                                                 _lib.ptr(out_s), _lib.ptr(out_r), _lib.current_stream()))
+    return out_s, out_r
+
   def _query_rows(self, queries, k: int, embedded: bool = False) -> Tuple[Tensor, Tensor]:
     st = self._indexed()
     q = queries if embedded else self._embed(queries)                   # :600-601
+    if q.dim() == 3:
+      return self._query_rows_heads(q, k)
     _check_query_dim(q, st.d)
     _check_k_against_rows(k, st.n)
     lib = _lib.load()

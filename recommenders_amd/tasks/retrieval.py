@@ -11,11 +11,14 @@ temperature (:187), sampling-probability correction (:190), accidental-hit remov
 ``batch_metrics`` (:228-232) of unadjusted logits are updated from rank counts
 (``TopKCategoricalAccuracy.update_from_embeddings``) and ``num_hard_negatives`` (:205-208) over
 plain dot-product logits from the fused top-K search (``hard_negative_softmax_loss``): neither
-builds the ``[num_queries, num_candidates]`` matrix.  What still needs the explicit matrix -- a
-user-supplied ``loss`` (its contract IS the matrix), multi-head (3-D) queries (:173-176), and
-batch metrics / hard negatives combined with a logit adjustment that can reorder a row
-(temperature for the metrics, sampling correction, accidental-hit removal, score mask) --
-computes it with the HIP dense GEMM and then follows the reference's op sequence on that tensor.
+builds the ``[num_queries, num_candidates]`` matrix.  Multi-head (3-D, max-sim) queries (:173-176)
+with up to 32 heads take the same fused route (``tfrs_inbatch_softmax_mh_ce_fwd/_bwd``: the max over
+heads is taken inside the kernels, the gradient of a pair goes to its lowest maximal head).  What
+still needs the explicit matrix -- a user-supplied ``loss`` (its contract IS the matrix), batch
+metrics / hard negatives combined with a logit adjustment that can reorder a row (temperature for
+the metrics, sampling correction, accidental-hit removal, score mask), and multi-head queries
+combined with hard negatives, batch metrics or more than 32 heads -- computes it with the HIP dense
+GEMM and then follows the reference's op sequence on that tensor.
 """
 
 import os
@@ -94,6 +97,80 @@ def in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: 
   mask = None if score_mask is None else score_mask.to(dev).to(torch.uint8).contiguous()
   return _InBatchSoftmaxFn.apply(query_embeddings.to(torch.float32),
                                  candidate_embeddings.to(torch.float32), w, inv_t, corr, ids, mask)
+
+
+MAX_FUSED_HEADS = 32   # head slots of a query share one 32-row MFMA block (csrc/softmax_mh.hip)
+
+
+class _MultiHeadSoftmaxFn(torch.autograd.Function):
+  """The same loss on logits ``max_h q_bh . c_c`` for queries ``[B, H, D]``; the gradient of a (query, candidate)
+  pair flows to the lowest head that attains the max."""
+
+  @staticmethod
+  def forward(ctx, q, c, sample_weight, inv_t, log_corr, cand_ids, score_mask):
+    lib = _lib.load()
+    q = q.contiguous()
+    c = c.contiguous()
+    nq, heads, d = q.shape
+    nc = c.shape[0]
+    ws = torch.empty((lib.tfrs_inbatch_softmax_mh_workspace_bytes(nq, heads, nc, d),),
+                     dtype=torch.uint8, device=q.device)
+    loss = torch.empty((), dtype=torch.float32, device=q.device)
+    lse = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    pos = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    _lib.check(lib.tfrs_inbatch_softmax_mh_ce_fwd(
+        _lib.ptr(q), _lib.ptr(c), nq, heads, nc, d, _lib.ptr(sample_weight), float(inv_t),
+        _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(loss),
+        _lib.ptr(lse), _lib.ptr(pos), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+    ctx.save_for_backward(q, c, sample_weight, log_corr, cand_ids, score_mask, lse)
+    ctx.inv_t = float(inv_t)
+    return loss
+
+  @staticmethod
+  def backward(ctx, gloss):
+    q, c, sample_weight, log_corr, cand_ids, score_mask, lse = ctx.saved_tensors
+    lib = _lib.load()
+    nq, heads, d = q.shape
+    nc = c.shape[0]
+    dq = torch.empty_like(q)
+    dc = torch.empty_like(c)
+    g = gloss.to(torch.float32).contiguous()
+    ws = torch.empty((lib.tfrs_inbatch_softmax_mh_workspace_bytes(nq, heads, nc, d),),
+                     dtype=torch.uint8, device=q.device)
+    _lib.check(lib.tfrs_inbatch_softmax_mh_ce_bwd(
+        _lib.ptr(q), _lib.ptr(c), nq, heads, nc, d, _lib.ptr(sample_weight), ctx.inv_t,
+        _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(lse),
+        _lib.ptr(g), _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+    return dq, dc, None, None, None, None, None
+
+
+def multi_head_in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
+                                     sample_weight: Optional[torch.Tensor] = None,
+                                     temperature: Optional[float] = None,
+                                     candidate_sampling_probability: Optional[torch.Tensor] = None,
+                                     candidate_ids: Optional[torch.Tensor] = None,
+                                     score_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """``in_batch_softmax_loss`` for multi-head queries ``[B, H, D]`` (retrieval.py:172-176): the logit of a
+  (query, candidate) pair is the max over the query's heads of the dot products, taken before the temperature
+  and the other adjustments.  ``H <= 32``, ``D <= 128``; no ``[B * H, C]`` or ``[B, C]`` tensor is built."""
+  if query_embeddings.dim() != 3:
+    raise ValueError(f"multi-head queries must be [B, H, D] (got {tuple(query_embeddings.shape)}).")
+  heads, d = query_embeddings.shape[1], query_embeddings.shape[2]
+  if not 1 <= heads <= MAX_FUSED_HEADS:
+    raise ValueError(f"multi_head_in_batch_softmax_loss: {heads} heads outside [1, {MAX_FUSED_HEADS}]")
+  if d > 128:
+    raise ValueError(f"multi_head_in_batch_softmax_loss: embedding dim {d} above 128")
+  dev = query_embeddings.device
+  inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
+  w = None if sample_weight is None else sample_weight.reshape(-1).to(dev, torch.float32).contiguous()
+  corr = None
+  if candidate_sampling_probability is not None:                      # loss.py:157-158
+    corr = torch.log(torch.clamp(candidate_sampling_probability.to(dev, torch.float32),
+                                 1e-6, 1.0)).contiguous()
+  ids = None if candidate_ids is None else candidate_ids.reshape(-1).to(dev).long().contiguous()
+  mask = None if score_mask is None else score_mask.to(dev).to(torch.uint8).contiguous()
+  return _MultiHeadSoftmaxFn.apply(query_embeddings.to(torch.float32),
+                                   candidate_embeddings.to(torch.float32), w, inv_t, corr, ids, mask)
 
 
 def hard_negative_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
@@ -399,7 +476,12 @@ class Retrieval(torch.nn.Module, base.Task):
         and candidate_sampling_probability is None and not self._remove_accidental_hits
         and score_mask is None and int(self._num_hard_negatives) + 2 <= 1024
         and not (compute_batch_metrics and len(self._batch_metrics) > 0))
-    need_matrix = (q.dim() == 3 or self._loss is not None
+    # multi-head queries: the fused max-sim kernels under the conditions of the 2-D fused route
+    fused_multi_head = (
+        q.dim() == 3 and self._loss is None and self._num_hard_negatives is None
+        and q.shape[-1] <= 128 and 1 <= q.shape[1] <= MAX_FUSED_HEADS
+        and not (compute_batch_metrics and len(self._batch_metrics) > 0))
+    need_matrix = ((q.dim() == 3 and not fused_multi_head) or self._loss is not None
                    or (self._num_hard_negatives is not None and not fused_hard_negatives) or wide
                    or (compute_batch_metrics and len(self._batch_metrics) > 0 and not fused_batch_metrics))
     scores = labels = None
@@ -409,6 +491,10 @@ class Retrieval(torch.nn.Module, base.Task):
 
     if self._loss is None and q.dim() == 2 and self._num_hard_negatives is None and not wide:
       loss = in_batch_softmax_loss(                                     # fused :172-210
+          q, c, sample_weight, self._temperature, candidate_sampling_probability,
+          candidate_ids if self._remove_accidental_hits else None, score_mask)
+    elif fused_multi_head:
+      loss = multi_head_in_batch_softmax_loss(                          # fused :172-176, :185-210
           q, c, sample_weight, self._temperature, candidate_sampling_probability,
           candidate_ids if self._remove_accidental_hits else None, score_mask)
     elif fused_hard_negatives:
