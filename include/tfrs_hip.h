@@ -451,6 +451,61 @@ int tfrs_table_update_dense_multi(int rule, const float *hyper_h, const float *a
                                   const float *const *grads_h, const int64_t *n_h, void *stream);
 int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2, int advance,
                    void *stream);
+/* Learning-rate schedules on the device (recommenders_amd/schedules.py): the learning rate of a step is a DEVICE float
+ * that a one-thread kernel at the head of the step writes from a DEVICE counter, so a captured step replays the whole
+ * schedule.  A schedule is a kind, a HOST array of 8 doubles and (kinds 0, 5, 6) a DEVICE f32 table of table_len entries;
+ * with s the counter as a double:
+ *   0 external      lr = table[0]: a device float the caller owns, re-read every step
+ *   1 exponential   {initial, decay_steps, decay_rate, staircase}: p = s / decay_steps, floored when staircase;
+ *                   lr = initial * decay_rate^p
+ *   2 inverse time  the same four: lr = initial / (1 + decay_rate * p)
+ *   3 polynomial    {initial, decay_steps, end, power, cycle}: x = min(s, decay_steps), ds = decay_steps, or with cycle
+ *                   x = s, ds = decay_steps * (s == 0 ? 1 : ceil(s / decay_steps)); lr = (initial - end) * (1 - x / ds)^power + end
+ *   4 cosine        {initial, decay_steps, alpha, has_warmup, warmup_target, warmup_steps}: with a warm-up and
+ *                   s < warmup_steps, lr = initial + (warmup_target - initial) * s / warmup_steps; else (the warm-up
+ *                   replacing initial by warmup_target and s by s - warmup_steps) x = min(s, decay_steps),
+ *                   lr = initial * ((1 - alpha) * 0.5 * (1 + cos(pi * x / decay_steps)) + alpha)
+ *   5 piecewise     params = table_len - 1 boundaries (1..7), table = values: table[i] for the smallest i with
+ *                   s <= boundary[i], else the last value
+ *   6 tabulated     table[min(counter, table_len - 1)]
+ * evaluated in float64 and rounded once to f32 (the table kinds copy an f32).
+ * tfrs_lr_tick: t = *iterations; lr_out[0] = schedule(t); with ftrl != 0 also
+ * lr_out[1] = (float)(2 * (l2 + beta / (2 * (double)lr_out[0]))), the third hyper-parameter of the Ftrl rule;
+ * *iterations = t + advance (0 or 1: the groups of one optimizer are all evaluated at the same t, the last one advances).
+ * tfrs_adam_tick_scheduled: tfrs_adam_tick whose learning rate is schedule(t - 1) for t = *step + advance -- Keras's
+ * iterations before the increment -- rounded to f32 into *lr_out; alpha is computed from that f32.
+ * The *_dlr entries are the update entries above with one more argument, lr_dev: NULL (then they ARE the entries
+ * above, which forward to them), or the device float of tfrs_lr_tick, which the kernels read once at entry in place of
+ * lr; the constant-lr kernels and the device-lr kernels are separate instantiations (the constant-lr ones are
+ * instruction for instruction what they were without the argument).  For tfrs_table_update_sparse / _dense_multi a
+ * non-NULL alpha with rule 0 (SGD) is that device float, with rule 2 (Ftrl) the two floats lr_out[0..1]; hyper_h[0] (and
+ * Ftrl's hyper_h[2]) are then not read -- the rule resolves it once at kernel entry, in the same instantiations.
+ * Every argument check comes before any device call. */
+int tfrs_lr_tick(int64_t *iterations, float *lr_out, int kind, const double *params_h, const float *table,
+                 int64_t table_len, int ftrl, double l2, double beta, int advance, void *stream);
+int tfrs_adam_tick_scheduled(int64_t *step, float *alpha, float *lr_out, int kind, const double *params_h,
+                             const float *table, int64_t table_len, double beta_1, double beta_2, int advance,
+                             void *stream);
+int tfrs_embedding_scatter_add_unsorted_dlr(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d,
+                                            int64_t vocab, float *grad_table_or_table, float *accum, float lr,
+                                            const float *lr_dev, float eps, int adagrad, void *workspace,
+                                            size_t workspace_bytes, void *stream);
+int tfrs_embedding_scatter_add_rowscan_dlr(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d,
+                                           int64_t vocab, float *grad_table_or_table, float *accum, float lr,
+                                           const float *lr_dev, float eps, int adagrad, void *stream);
+int tfrs_embedding_scatter_add_rowscan_multi_dlr(int ntables, const float *const *grad_out_h, const void *const *ids_h,
+                                                 const int *ids_are_i64_h, const int64_t *n_h, const int *d_h,
+                                                 const int64_t *vocab_h, float *const *tables_h, float *const *accum_h,
+                                                 float lr, const float *lr_dev, float eps, int adagrad, void *stream);
+int tfrs_adagrad_dense_multi_dlr(int ntensors, float *const *params_h, float *const *accum_h, const float *const *grads_h,
+                                 const int64_t *n_h, float lr, const float *lr_dev, float eps, int mode, void *stream);
+int tfrs_clippy_dense_multi_dlr(int ntensors, float *const *params_h, float *const *accum_h, const float *const *grads_h,
+                                const int64_t *n_h, float *factors, float lr, const float *lr_dev, float eps,
+                                float var_rel, float acc_rel, float abs_thr, int mode, void *stream);
+int tfrs_clippy_sparse_dlr(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d, int64_t vocab,
+                           float *table, float *accum, float *factor, float lr, const float *lr_dev, float eps,
+                           float var_rel, float acc_rel, float abs_thr, int mode, int rowscan, void *workspace,
+                           size_t workspace_bytes, void *stream);
 /* Up to 16 device buffers copied in ONE launch: a batch's input tensors into the static buffers of a captured
  * train / test step (the `Model.fit` loop of models/base.py:64-85 replays HIP graphs; README.md:84-98).  Host arrays of
  * device pointers and byte counts; buffers must not overlap. */

@@ -97,6 +97,19 @@ SIGNATURES = {
     "tfrs_table_update_dense_multi": (c_int, [c_int, P, P, c_int, P, P, P, P, P, P]),
     "tfrs_adam_tick": (c_int, [P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, P]),
     "tfrs_copy_multi": (c_int, [c_int, P, P, P, P]),
+    "tfrs_lr_tick": (c_int, [P, P, c_int, P, P, c_i64, c_int, ctypes.c_double, ctypes.c_double, c_int, P]),
+    "tfrs_adam_tick_scheduled": (c_int, [P, P, P, c_int, P, P, c_i64, ctypes.c_double, ctypes.c_double, c_int, P]),
+    "tfrs_embedding_scatter_add_unsorted_dlr": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, c_float, P,
+                                                        c_float, c_int, P, c_size_t, P]),
+    "tfrs_embedding_scatter_add_rowscan_dlr": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, c_float, P,
+                                                       c_float, c_int, P]),
+    "tfrs_embedding_scatter_add_rowscan_multi_dlr": (c_int, [c_int, P, P, P, P, P, P, P, P, c_float, P, c_float,
+                                                             c_int, P]),
+    "tfrs_adagrad_dense_multi_dlr": (c_int, [c_int, P, P, P, P, c_float, P, c_float, c_int, P]),
+    "tfrs_clippy_dense_multi_dlr": (c_int, [c_int, P, P, P, P, P, c_float, P, c_float, c_float, c_float, c_float,
+                                            c_int, P]),
+    "tfrs_clippy_sparse_dlr": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, P, c_float, P, c_float, c_float,
+                                       c_float, c_float, c_int, c_int, P, c_size_t, P]),
     "tfrs_embedding_scatter_add_rowscan": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, c_float,
                                                    c_float, c_int, P]),
     "tfrs_inbatch_softmax_workspace_bytes": (c_size_t, [c_i64, c_i64, c_int]),

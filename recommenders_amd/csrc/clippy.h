@@ -18,6 +18,19 @@ namespace tfrs {
 struct ClippyHyper {
   float lr, eps, var_rel, acc_rel, abs_thr;
   int mode;
+  __device__ __forceinline__ ClippyHyper get() const { return *this; }
+};
+
+// ClippyHyper whose lr is read (once, at kernel entry) from the device float of tfrs_lr_tick: the kernels are templates
+// over the two, so a constant float learning rate keeps its own instantiations
+struct ClippyHyperDevice {
+  ClippyHyper h;
+  const float *lr;
+  __device__ __forceinline__ ClippyHyper get() const {
+    ClippyHyper r = h;
+    r.lr = *lr;
+    return r;
+  }
 };
 
 struct ClippyElement {

@@ -20,9 +20,10 @@ struct ClippyDenseTensors {
 };
 constexpr int kClippyPerBlock = 256 * 16;
 
-template <bool APPLY>
+template <bool APPLY, typename HYPER = ClippyHyper>
 __global__ void __launch_bounds__(256) clippy_dense_multi_kernel(const ClippyDenseTensors t, float *__restrict__ factors,
-                                                                 const ClippyHyper h) {
+                                                                 const HYPER h_arg) {
+  const ClippyHyper h = h_arg.get();
   int k = 0;
   while (k + 1 < t.ntensors && (int)blockIdx.x >= t.first_block[k + 1]) ++k;
   float *__restrict__ p = t.p[k];
@@ -87,6 +88,15 @@ extern "C" int tfrs_clippy_dense_multi(int ntensors, float *const *params_h, flo
                                        const float *const *grads_h, const int64_t *n_h, float *factors, float lr,
                                        float eps, float var_rel, float acc_rel, float abs_thr, int mode,
                                        void *stream) {
+  return tfrs_clippy_dense_multi_dlr(ntensors, params_h, accum_h, grads_h, n_h, factors, lr, nullptr, eps, var_rel,
+                                     acc_rel, abs_thr, mode, stream);
+}
+
+// (lr_dev: NULL, or the device float of tfrs_lr_tick, read by both passes in place of lr)
+extern "C" int tfrs_clippy_dense_multi_dlr(int ntensors, float *const *params_h, float *const *accum_h,
+                                           const float *const *grads_h, const int64_t *n_h, float *factors, float lr,
+                                           const float *lr_dev, float eps, float var_rel, float acc_rel, float abs_thr,
+                                           int mode, void *stream) {
   using namespace tfrs;
   TFRS_CHECK_ARG(ntensors >= 1 && ntensors <= 32, "clippy_dense_multi: 1..32 tensors");
   TFRS_CHECK_ARG(params_h && accum_h && grads_h && n_h && factors, "clippy_dense_multi: NULL argument");
@@ -107,9 +117,13 @@ extern "C" int tfrs_clippy_dense_multi(int ntensors, float *const *params_h, flo
   const ClippyHyper h = {lr, eps, var_rel, acc_rel, abs_thr, mode};
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(clippy_arm_kernel, dim3(1), dim3(64), 0, s, factors, ntensors);
-  if (blocks > 0) {
-    hipLaunchKernelGGL(clippy_dense_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, t, factors, h);
-    hipLaunchKernelGGL(clippy_dense_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, t, factors, h);
+  if (blocks > 0 && lr_dev) {
+    const ClippyHyperDevice hd = {h, lr_dev};
+    hipLaunchKernelGGL((clippy_dense_multi_kernel<false, ClippyHyperDevice>), dim3((unsigned)blocks), dim3(256), 0, s, t, factors, hd);
+    hipLaunchKernelGGL((clippy_dense_multi_kernel<true, ClippyHyperDevice>), dim3((unsigned)blocks), dim3(256), 0, s, t, factors, hd);
+  } else if (blocks > 0) {
+    hipLaunchKernelGGL((clippy_dense_multi_kernel<false, ClippyHyper>), dim3((unsigned)blocks), dim3(256), 0, s, t, factors, h);
+    hipLaunchKernelGGL((clippy_dense_multi_kernel<true, ClippyHyper>), dim3((unsigned)blocks), dim3(256), 0, s, t, factors, h);
   }
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;

@@ -501,13 +501,14 @@ __device__ __forceinline__ void scatter_rowscan_body(
   else scatter_rowscan_body_ns<IdT, 4>(grad_out, ids, n, d, vocab, dst, accum, lr, eps, adagrad, block, s_ids, s_hits);
 }
 
-template <typename IdT>
+template <typename IdT, typename LR = LrValue>
 __global__ void __launch_bounds__(256) scatter_rowscan_kernel(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d,
-    int64_t vocab, float *__restrict__ dst, float *__restrict__ accum, float lr, float eps,
+    int64_t vocab, float *__restrict__ dst, float *__restrict__ accum, const LR lr_arg, float eps,
     int adagrad) {
   __shared__ int32_t s_ids[kRowscanChunk];
   __shared__ int s_hits[4 * kRowscanHitCap];
+  const float lr = lr_arg.get();
   scatter_rowscan_body<IdT>(grad_out, ids, n, d, vocab, dst, accum, lr, eps, adagrad, blockIdx.x, s_ids, s_hits);
 }
 
@@ -526,8 +527,10 @@ struct RowscanTables {
   float *accum[8];
   int i64[8];
 };
-__global__ void __launch_bounds__(256) scatter_rowscan_multi_kernel(const RowscanTables t, float lr, float eps,
+template <typename LR = LrValue>
+__global__ void __launch_bounds__(256) scatter_rowscan_multi_kernel(const RowscanTables t, const LR lr_arg, float eps,
                                                                     int adagrad) {
+  const float lr = lr_arg.get();
   int k = 0;
 #pragma unroll
   for (int i = 1; i < 8; ++i)
@@ -878,12 +881,14 @@ __global__ void __launch_bounds__(256) scatter_add_pieces_kernel(
 // NT: the gradient rows, the table / accumulator rows and their stores carry the non-temporal hint -- every one of them
 // is touched once per launch, and a table beyond the last-level cache (the launcher asks for > 1 GiB) gains nothing from
 // keeping them: 26 M x 128, 1.7 M ids, same box, alternating: 0.960 -> 0.933 ms (the loads alone 0.943, the stores alone +-0).
-template <int VEC, bool NT = false>
+// LR: LrValue (the learning rate by value) or LrDevice (read once from the device float of tfrs_lr_tick), table_rules.h
+template <int VEC, bool NT = false, typename LR = LrValue>
 __global__ void __launch_bounds__(256) scatter_add_u32_kernel(
     const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids,
     const uint32_t *__restrict__ perm, int64_t n, int d, uint32_t vocab, float *__restrict__ dst,
-    float *__restrict__ accum, float lr, float eps, int adagrad, int piece,
+    float *__restrict__ accum, const LR lr_arg, float eps, int adagrad, int piece,
     const float *__restrict__ part) {
+  const float lr = lr_arg.get();
   const int per_row = d / VEC;
   const int64_t total = n * per_row;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
@@ -1055,6 +1060,16 @@ extern "C" int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const 
                                                    float *grad_table_or_table, float *accum, float lr,
                                                    float eps, int adagrad, void *workspace,
                                                    size_t workspace_bytes, void *stream) {
+  return tfrs_embedding_scatter_add_unsorted_dlr(grad_out, ids, ids_are_i64, n, d, vocab, grad_table_or_table, accum,
+                                                 lr, nullptr, eps, adagrad, workspace, workspace_bytes, stream);
+}
+
+// (lr_dev: NULL, or the device float of tfrs_lr_tick, read by the Adagrad epilogue in place of lr)
+extern "C" int tfrs_embedding_scatter_add_unsorted_dlr(const float *grad_out, const void *ids,
+                                                       int ids_are_i64, int64_t n, int d, int64_t vocab,
+                                                       float *grad_table_or_table, float *accum, float lr,
+                                                       const float *lr_dev, float eps, int adagrad, void *workspace,
+                                                       size_t workspace_bytes, void *stream) {
   using namespace tfrs;
   TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "embedding_scatter_add_unsorted: bad shape");
   TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll,
@@ -1082,22 +1097,27 @@ extern "C" int tfrs_embedding_scatter_add_unsorted(const float *grad_out, const 
   float *part = reinterpret_cast<float *>(keys[cur ^ 1]);
   const int64_t ptotal = ((n + piece - 1) / piece) * (vec ? d / 4 : d);
   const dim3 pgrid(grid_for(ptotal, 256 * 64));
-  if (vec) {
-    hipLaunchKernelGGL((scatter_add_pieces_kernel<4>), pgrid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
-                       (uint32_t)vocab, piece, part);
-    const char *nte = option("TFRS_SCATTER_NT");
-    if (vocab * (int64_t)d * 4 > (1ll << 30) && !(nte && nte[0] == '0'))
-      hipLaunchKernelGGL((scatter_add_u32_kernel<4, true>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
-                         (uint32_t)vocab, grad_table_or_table, accum, lr, eps, adagrad, piece, part);
-    else
-      hipLaunchKernelGGL((scatter_add_u32_kernel<4>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
-                         (uint32_t)vocab, grad_table_or_table, accum, lr, eps, adagrad, piece, part);
-  } else {
-    hipLaunchKernelGGL((scatter_add_pieces_kernel<1>), pgrid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
-                       (uint32_t)vocab, piece, part);
-    hipLaunchKernelGGL((scatter_add_u32_kernel<1>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
-                       (uint32_t)vocab, grad_table_or_table, accum, lr, eps, adagrad, piece, part);
-  }
+  auto launch = [&](auto lr_arg) {
+    using LR = decltype(lr_arg);
+    if (vec) {
+      hipLaunchKernelGGL((scatter_add_pieces_kernel<4>), pgrid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
+                         (uint32_t)vocab, piece, part);
+      const char *nte = option("TFRS_SCATTER_NT");
+      if (vocab * (int64_t)d * 4 > (1ll << 30) && !(nte && nte[0] == '0'))
+        hipLaunchKernelGGL((scatter_add_u32_kernel<4, true, LR>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
+                           (uint32_t)vocab, grad_table_or_table, accum, lr_arg, eps, adagrad, piece, part);
+      else
+        hipLaunchKernelGGL((scatter_add_u32_kernel<4, false, LR>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
+                           (uint32_t)vocab, grad_table_or_table, accum, lr_arg, eps, adagrad, piece, part);
+    } else {
+      hipLaunchKernelGGL((scatter_add_pieces_kernel<1>), pgrid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
+                         (uint32_t)vocab, piece, part);
+      hipLaunchKernelGGL((scatter_add_u32_kernel<1, false, LR>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d,
+                         (uint32_t)vocab, grad_table_or_table, accum, lr_arg, eps, adagrad, piece, part);
+    }
+  };
+  if (lr_dev) launch(LrDevice{lr_dev});
+  else launch(LrValue{lr});
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -1117,8 +1137,10 @@ struct DenseAdagradTensors {
   int64_t n[32];
 };
 constexpr int kDenseAdagradPerBlock = 256 * 16;
-__global__ void __launch_bounds__(256) adagrad_dense_multi_kernel(const DenseAdagradTensors t, float lr, float eps,
+template <typename LR = LrValue>
+__global__ void __launch_bounds__(256) adagrad_dense_multi_kernel(const DenseAdagradTensors t, const LR lr_arg, float eps,
                                                                   int mode) {
+  const float lr = lr_arg.get();
   int k = 0;
   while (k + 1 < t.ntensors && (int)blockIdx.x >= t.first_block[k + 1]) ++k;
   float *__restrict__ p = t.p[k];
@@ -1161,6 +1183,12 @@ __global__ void __launch_bounds__(256) adagrad_dense_multi_kernel(const DenseAda
 extern "C" int tfrs_adagrad_dense_multi(int ntensors, float *const *params_h, float *const *accum_h,
                                         const float *const *grads_h, const int64_t *n_h, float lr, float eps,
                                         int mode, void *stream) {
+  return tfrs_adagrad_dense_multi_dlr(ntensors, params_h, accum_h, grads_h, n_h, lr, nullptr, eps, mode, stream);
+}
+
+extern "C" int tfrs_adagrad_dense_multi_dlr(int ntensors, float *const *params_h, float *const *accum_h,
+                                            const float *const *grads_h, const int64_t *n_h, float lr,
+                                            const float *lr_dev, float eps, int mode, void *stream) {
   TFRS_CHECK_ARG(ntensors >= 1 && ntensors <= 32, "adagrad_dense_multi: 1..32 tensors");
   TFRS_CHECK_ARG(params_h && accum_h && grads_h && n_h, "adagrad_dense_multi: NULL argument array");
   TFRS_CHECK_ARG(mode == 1 || mode == 2, "adagrad_dense_multi: mode must be 1 (sqrt(acc + eps)) or 2 (sqrt(acc) + eps)");
@@ -1177,8 +1205,12 @@ extern "C" int tfrs_adagrad_dense_multi(int ntensors, float *const *params_h, fl
   }
   t.first_block[ntensors] = (int)blocks;
   if (blocks == 0) return TFRS_OK;
-  hipLaunchKernelGGL(tfrs::adagrad_dense_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, lr,
-                     eps, mode);
+  if (lr_dev)
+    hipLaunchKernelGGL(tfrs::adagrad_dense_multi_kernel<tfrs::LrDevice>, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, t, tfrs::LrDevice{lr_dev}, eps, mode);
+  else
+    hipLaunchKernelGGL(tfrs::adagrad_dense_multi_kernel<tfrs::LrValue>, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, t, tfrs::LrValue{lr}, eps, mode);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -1254,6 +1286,17 @@ extern "C" int tfrs_embedding_scatter_add_rowscan_multi(int ntables, const float
                                                         float *const *tables_h, float *const *accum_h,
                                                         float lr, float eps, int adagrad,
                                                         void *stream) {
+  return tfrs_embedding_scatter_add_rowscan_multi_dlr(ntables, grad_out_h, ids_h, ids_are_i64_h, n_h, d_h, vocab_h,
+                                                      tables_h, accum_h, lr, nullptr, eps, adagrad, stream);
+}
+
+extern "C" int tfrs_embedding_scatter_add_rowscan_multi_dlr(int ntables, const float *const *grad_out_h,
+                                                            const void *const *ids_h,
+                                                            const int *ids_are_i64_h, const int64_t *n_h,
+                                                            const int *d_h, const int64_t *vocab_h,
+                                                            float *const *tables_h, float *const *accum_h,
+                                                            float lr, const float *lr_dev, float eps, int adagrad,
+                                                            void *stream) {
   TFRS_CHECK_ARG(ntables >= 1 && ntables <= 8, "embedding_scatter_add_rowscan_multi: 1..8 tables");
   TFRS_CHECK_ARG(grad_out_h && ids_h && ids_are_i64_h && n_h && d_h && vocab_h && tables_h,
                  "embedding_scatter_add_rowscan_multi: NULL argument array");
@@ -1272,8 +1315,12 @@ extern "C" int tfrs_embedding_scatter_add_rowscan_multi(int ntables, const float
     t.i64[i] = ids_are_i64_h[i];
   }
   t.first_block[ntables] = blocks;
-  hipLaunchKernelGGL(tfrs::scatter_rowscan_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     t, lr, eps, adagrad);
+  if (lr_dev)
+    hipLaunchKernelGGL(tfrs::scatter_rowscan_multi_kernel<tfrs::LrDevice>, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, t, tfrs::LrDevice{lr_dev}, eps, adagrad);
+  else
+    hipLaunchKernelGGL(tfrs::scatter_rowscan_multi_kernel<tfrs::LrValue>, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, t, tfrs::LrValue{lr}, eps, adagrad);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -1283,16 +1330,31 @@ extern "C" int tfrs_embedding_scatter_add_rowscan(const float *grad_out, const v
                                                   int64_t vocab, float *grad_table_or_table,
                                                   float *accum, float lr, float eps, int adagrad,
                                                   void *stream) {
+  return tfrs_embedding_scatter_add_rowscan_dlr(grad_out, ids, ids_are_i64, n, d, vocab, grad_table_or_table, accum, lr,
+                                                nullptr, eps, adagrad, stream);
+}
+
+extern "C" int tfrs_embedding_scatter_add_rowscan_dlr(const float *grad_out, const void *ids,
+                                                      int ids_are_i64, int64_t n, int d,
+                                                      int64_t vocab, float *grad_table_or_table,
+                                                      float *accum, float lr, const float *lr_dev, float eps,
+                                                      int adagrad, void *stream) {
+  using namespace tfrs;
   TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "embedding_scatter_add_rowscan: bad shape");
   TFRS_CHECK_ARG(d <= 256, "embedding_scatter_add_rowscan: d=%d > 256 (use the sorted path)", d);
   TFRS_CHECK_ARG((n == 0 || (grad_out && ids)) && grad_table_or_table,
                  "embedding_scatter_add_rowscan: NULL pointer");
   TFRS_CHECK_ARG(!adagrad || accum, "embedding_scatter_add_rowscan: Adagrad needs an accumulator");
   const dim3 grid((unsigned)((vocab + 3) / 4)), block(256);
-  if (ids_are_i64)
-    hipLaunchKernelGGL((scatter_rowscan_kernel<int64_t>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr, eps, adagrad);
-  else
-    hipLaunchKernelGGL((scatter_rowscan_kernel<int32_t>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr, eps, adagrad);
+  auto launch = [&](auto lr_arg) {
+    using LR = decltype(lr_arg);
+    if (ids_are_i64)
+      hipLaunchKernelGGL((scatter_rowscan_kernel<int64_t, LR>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr_arg, eps, adagrad);
+    else
+      hipLaunchKernelGGL((scatter_rowscan_kernel<int32_t, LR>), grid, block, 0, (hipStream_t)stream, grad_out, ids, n, d, vocab, grad_table_or_table, accum, lr_arg, eps, adagrad);
+  };
+  if (lr_dev) launch(LrDevice{lr_dev});
+  else launch(LrValue{lr});
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -1308,11 +1370,12 @@ extern "C" int tfrs_embedding_scatter_add_rowscan(const float *grad_out, const v
 // error bound is stated against the sequential f32 sum.
 namespace tfrs {
 
-template <int VEC, bool APPLY>
+template <int VEC, bool APPLY, typename HYPER = ClippyHyper>
 __global__ void __launch_bounds__(256) clippy_sorted_kernel(
     const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids, const uint32_t *__restrict__ perm,
     int64_t n, int d, uint32_t vocab, float *__restrict__ table, float *__restrict__ accum,
-    float *__restrict__ factor_slot, const ClippyHyper h) {
+    float *__restrict__ factor_slot, const HYPER h_arg) {
+  const ClippyHyper h = h_arg.get();
   const int per_row = d / VEC;
   const int64_t total = n * per_row;
   const float factor = APPLY ? *factor_slot : 1.0f;
@@ -1392,12 +1455,13 @@ __global__ void __launch_bounds__(256) clippy_sorted_kernel(
   }
 }
 
-template <typename IdT, bool APPLY>
+template <typename IdT, bool APPLY, typename HYPER = ClippyHyper>
 __global__ void __launch_bounds__(256) clippy_rowscan_kernel(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d, int64_t vocab,
-    float *__restrict__ table, float *__restrict__ accum, float *__restrict__ factor_slot, const ClippyHyper h) {
+    float *__restrict__ table, float *__restrict__ accum, float *__restrict__ factor_slot, const HYPER h_arg) {
   __shared__ int32_t s_ids[kRowscanChunk];
   __shared__ int s_hits[4 * kRowscanHitCap];
+  const ClippyHyper h = h_arg.get();
   constexpr int PASS = APPLY ? 2 : 1;
   if (d <= 64) scatter_rowscan_body_ns<IdT, 1, PASS>(grad_out, ids, n, d, vocab, table, accum, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, factor_slot, &h);
   else if (d <= 128) scatter_rowscan_body_ns<IdT, 2, PASS>(grad_out, ids, n, d, vocab, table, accum, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, factor_slot, &h);
@@ -1414,6 +1478,14 @@ extern "C" int tfrs_clippy_sparse(const float *grad_out, const void *ids, int id
                                   int64_t vocab, float *table, float *accum, float *factor, float lr, float eps,
                                   float var_rel, float acc_rel, float abs_thr, int mode, int rowscan,
                                   void *workspace, size_t workspace_bytes, void *stream) {
+  return tfrs_clippy_sparse_dlr(grad_out, ids, ids_are_i64, n, d, vocab, table, accum, factor, lr, nullptr, eps, var_rel,
+                                acc_rel, abs_thr, mode, rowscan, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tfrs_clippy_sparse_dlr(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d,
+                                      int64_t vocab, float *table, float *accum, float *factor, float lr,
+                                      const float *lr_dev, float eps, float var_rel, float acc_rel, float abs_thr,
+                                      int mode, int rowscan, void *workspace, size_t workspace_bytes, void *stream) {
   using namespace tfrs;
   TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "clippy_sparse: bad shape");
   TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll, "clippy_sparse: vocab / n must fit 32 bits");
@@ -1431,13 +1503,18 @@ extern "C" int tfrs_clippy_sparse(const float *grad_out, const void *ids, int id
   TFRS_CHECK_ARG(grad_out && ids, "clippy_sparse: NULL pointer");
   if (rowscan) {
     const dim3 grid((unsigned)((vocab + 3) / 4)), block(256);
-    if (ids_are_i64) {
-      hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, false>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
-      hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, true>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
-    } else {
-      hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, false>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
-      hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, true>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, h);
-    }
+    auto launch = [&](auto ha) {
+      using H = decltype(ha);
+      if (ids_are_i64) {
+        hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, false, H>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, ha);
+        hipLaunchKernelGGL((clippy_rowscan_kernel<int64_t, true, H>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, ha);
+      } else {
+        hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, false, H>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, ha);
+        hipLaunchKernelGGL((clippy_rowscan_kernel<int32_t, true, H>), grid, block, 0, s, grad_out, ids, n, d, vocab, table, accum, factor, ha);
+      }
+    };
+    if (lr_dev) launch(ClippyHyperDevice{h, lr_dev});
+    else launch(h);
     TFRS_LAUNCH_CHECK();
     return TFRS_OK;
   }
@@ -1453,13 +1530,18 @@ extern "C" int tfrs_clippy_sparse(const float *grad_out, const void *ids, int id
                    (((uintptr_t)accum) % 16 == 0);
   const int64_t total = n * (vec ? d / 4 : d);
   const dim3 grid(grid_for(total, 256 * 64)), block(256);
-  if (vec) {
-    hipLaunchKernelGGL((clippy_sorted_kernel<4, false>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
-    hipLaunchKernelGGL((clippy_sorted_kernel<4, true>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
-  } else {
-    hipLaunchKernelGGL((clippy_sorted_kernel<1, false>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
-    hipLaunchKernelGGL((clippy_sorted_kernel<1, true>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, h);
-  }
+  auto launch = [&](auto ha) {
+    using H = decltype(ha);
+    if (vec) {
+      hipLaunchKernelGGL((clippy_sorted_kernel<4, false, H>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, ha);
+      hipLaunchKernelGGL((clippy_sorted_kernel<4, true, H>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, ha);
+    } else {
+      hipLaunchKernelGGL((clippy_sorted_kernel<1, false, H>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, ha);
+      hipLaunchKernelGGL((clippy_sorted_kernel<1, true, H>), grid, block, 0, s, grad_out, keys[cur], vals[cur], n, d, (uint32_t)vocab, table, accum, factor, ha);
+    }
+  };
+  if (lr_dev) launch(ClippyHyperDevice{h, lr_dev});
+  else launch(h);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -1476,7 +1558,8 @@ template <typename RULE, int VEC, bool NT>
 __global__ void __launch_bounds__(256) table_update_sorted_kernel(
     const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids, const uint32_t *__restrict__ perm,
     int64_t n, int d, uint32_t vocab, float *__restrict__ table, float *__restrict__ slot0, float *__restrict__ slot1,
-    const RULE rule, int piece, const float *__restrict__ part) {
+    const RULE rule_arg, int piece, const float *__restrict__ part) {
+  const RULE rule = rule_arg.resolved();
   const int per_row = d / VEC;
   const int64_t total = n * per_row;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
@@ -1549,9 +1632,10 @@ __global__ void __launch_bounds__(256) table_update_sorted_kernel(
 template <typename RULE, typename IdT>
 __global__ void __launch_bounds__(256) table_update_rowscan_kernel(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d, int64_t vocab,
-    float *__restrict__ table, float *__restrict__ slot0, float *__restrict__ slot1, const RULE rule) {
+    float *__restrict__ table, float *__restrict__ slot0, float *__restrict__ slot1, const RULE rule_arg) {
   __shared__ int32_t s_ids[kRowscanChunk];
   __shared__ int s_hits[4 * kRowscanHitCap];
+  const RULE rule = rule_arg.resolved();
   if (d <= 64) scatter_rowscan_body_ns<IdT, 1, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
   else if (d <= 128) scatter_rowscan_body_ns<IdT, 2, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
   else scatter_rowscan_body_ns<IdT, 4, 0, RULE>(grad_out, ids, n, d, vocab, table, slot0, 0.f, 0.f, 0, blockIdx.x, s_ids, s_hits, nullptr, nullptr, &rule, slot1);
@@ -1640,8 +1724,9 @@ extern "C" int tfrs_table_update_sparse(int rule, const float *hyper_h, const fl
   }
   const SparseUpdateArgs a = {grad_out, ids, ids_are_i64, n, d, vocab, table, slot0, slot1, rowscan, workspace,
                               (hipStream_t)stream};
-  if (rule == kRuleSgd) return table_update_sparse_launch(a, SgdRule{hyper_h[0]});
+  // (for SGD and Ftrl a non-NULL alpha is the device floats of tfrs_lr_tick)
+  if (rule == kRuleSgd) return table_update_sparse_launch(a, SgdRule{hyper_h[0], alpha});
   if (rule == kRuleAdam) return table_update_sparse_launch(a, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha});
-  if (hyper_h[4] != 0.0f) return table_update_sparse_launch(a, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]});
-  return table_update_sparse_launch(a, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]});
+  if (hyper_h[4] != 0.0f) return table_update_sparse_launch(a, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha});
+  return table_update_sparse_launch(a, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha});
 }

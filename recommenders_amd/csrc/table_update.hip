@@ -1,6 +1,6 @@
 // optimizers.SGD / Adam / Ftrl on dense parameters (one launch for up to 32 tensors, the layout of
-// adagrad_dense_multi_kernel with the rule of table_rules.h as a template parameter) and Adam's device-side step
-// counter.  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
+// adagrad_dense_multi_kernel with the rule of table_rules.h as a template parameter), Adam's device-side step
+// counter, and the learning-rate schedules every optimizer evaluates on the device (lr_tick_kernel).  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
 #include "common.h"
 #include "table_rules.h"
 
@@ -20,7 +20,8 @@ constexpr int kDenseUpdatePerBlock = 256 * 16;
 // tensor t owns blocks [first_block[t], first_block[t + 1]) of 256 threads x 4 x float4; a tensor that is not 16-byte
 // aligned, and the block in which a tensor ends, take the scalar loop
 template <typename RULE>
-__global__ void __launch_bounds__(256) table_update_dense_multi_kernel(const DenseUpdateTensors t, const RULE rule) {
+__global__ void __launch_bounds__(256) table_update_dense_multi_kernel(const DenseUpdateTensors t, const RULE rule_arg) {
+  const RULE rule = rule_arg.resolved();
   int k = 0;
   while (k + 1 < t.ntensors && (int)blockIdx.x >= t.first_block[k + 1]) ++k;
   float *__restrict__ p = t.p[k];
@@ -71,13 +72,79 @@ static int table_update_dense_launch(const DenseUpdateTensors &t, int64_t blocks
   return TFRS_OK;
 }
 
+// ---- learning-rate schedules on the device -------------------------------------------------------------------------
+// recommenders_amd/schedules.py describes a schedule as a kind, 8 doubles and an optional f32 table; the kernels below
+// evaluate it in float64 at the device counter and round ONCE to f32, so a captured step replays the whole schedule.
+//   kind 0  external      lr = table[0] (a device float the user owns, re-read every step)
+//        1  exponential   p = {initial, decay_steps, decay_rate, staircase}
+//        2  inverse time  p = {initial, decay_steps, decay_rate, staircase}
+//        3  polynomial    p = {initial, decay_steps, end, power, cycle}
+//        4  cosine        p = {initial, decay_steps, alpha, has_warmup, warmup_target, warmup_steps}
+//        5  piecewise     p = boundaries (table_len - 1 of them, at most 7), table = values
+//        6  tabulated     table[min(t, table_len - 1)]
+enum { kLrExternal = 0, kLrExponential, kLrInverseTime, kLrPolynomial, kLrCosine, kLrPiecewise, kLrTabulated, kLrKinds };
+
+struct LrSchedule {
+  int kind;
+  double p[8];
+  const float *table;
+  int64_t table_len;
+};
+
+__device__ static float lr_schedule_eval(const LrSchedule &s, int64_t t) {
+  if (t < 0) t = 0;
+  const double step = (double)t;
+  switch (s.kind) {
+    case kLrExternal:
+      return s.table[0];
+    case kLrExponential:
+    case kLrInverseTime: {
+      double p = step / s.p[1];
+      if (s.p[3] != 0.0) p = floor(p);
+      return (float)(s.kind == kLrExponential ? s.p[0] * pow(s.p[2], p) : s.p[0] / (1.0 + s.p[2] * p));
+    }
+    case kLrPolynomial: {
+      double x = step, ds = s.p[1];
+      if (s.p[4] != 0.0) ds = ds * (t == 0 ? 1.0 : ceil(step / ds));
+      else x = fmin(step, ds);
+      return (float)((s.p[0] - s.p[2]) * pow(1.0 - x / ds, s.p[3]) + s.p[2]);
+    }
+    case kLrCosine: {
+      double initial = s.p[0], x = step;
+      if (s.p[3] != 0.0) {
+        if (step < s.p[5]) return (float)(s.p[0] + (s.p[4] - s.p[0]) * step / s.p[5]);
+        initial = s.p[4];
+        x = step - s.p[5];
+      }
+      x = fmin(x, s.p[1]);
+      const double pi = 3.141592653589793;
+      return (float)(initial * ((1.0 - s.p[2]) * 0.5 * (1.0 + cos(pi * x / s.p[1])) + s.p[2]));
+    }
+    case kLrPiecewise: {
+      const int nb = (int)s.table_len - 1;
+      for (int i = 0; i < nb; ++i)
+        if (step <= s.p[i]) return s.table[i];
+      return s.table[nb];
+    }
+    default:   // kLrTabulated
+      return s.table[t < s.table_len - 1 ? t : s.table_len - 1];
+  }
+}
+
 // One thread: t += advance;  alpha = lr * sqrt(1 - beta_2^t) / (1 - beta_1^t) in float64 from the integer t (powers by
 // repeated squaring: at most 2 * 63 products), rounded once to f32.  t is Keras's iterations + 1.
+// With lr_out (tfrs_adam_tick_scheduled) the learning rate is the schedule `s` at t - 1 -- Keras's iterations before the
+// increment -- rounded to f32 into *lr_out, and alpha is computed from that f32.
 __global__ void adam_tick_kernel(int64_t *__restrict__ step, float *__restrict__ alpha, double lr, double beta_1,
-                                 double beta_2, int advance) {
+                                 double beta_2, int advance, float *__restrict__ lr_out, const LrSchedule s) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const int64_t t = *step + advance;
   if (advance) *step = t;
+  if (lr_out) {
+    const float scheduled = lr_schedule_eval(s, t - 1);
+    *lr_out = scheduled;
+    lr = (double)scheduled;
+  }
   double p1 = 1.0, p2 = 1.0, b1 = beta_1, b2 = beta_2;
   for (int64_t e = t; e > 0; e >>= 1) {
     if (e & 1) {
@@ -88,6 +155,39 @@ __global__ void adam_tick_kernel(int64_t *__restrict__ step, float *__restrict__
     b2 *= b2;
   }
   *alpha = (float)(lr * sqrt(1.0 - p2) / (1.0 - p1));
+}
+
+// One thread: lr_out[0] = schedule(*iterations); Ftrl also gets lr_out[1] = 2 * (l2 + beta / (2 lr)) from that f32 lr
+// (what Ftrl._hyper computes on the host from a float learning rate); then *iterations += advance.
+__global__ void lr_tick_kernel(int64_t *__restrict__ iterations, float *__restrict__ lr_out, const LrSchedule s,
+                               int ftrl, double l2, double beta, int advance) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t t = *iterations;
+  const float lr = lr_schedule_eval(s, t);
+  lr_out[0] = lr;
+  if (ftrl) lr_out[1] = (float)(2.0 * (l2 + beta / (2.0 * (double)lr)));
+  if (advance) *iterations = t + advance;
+}
+
+// (before any device call)
+static int lr_schedule_check(const char *who, int kind, const double *params_h, const float *table, int64_t table_len,
+                             LrSchedule *out) {
+  TFRS_CHECK_ARG(kind >= 0 && kind < kLrKinds, "%s: unknown schedule kind %d", who, kind);
+  TFRS_CHECK_ARG(params_h, "%s: NULL schedule parameters", who);
+  if (kind == kLrExternal || kind == kLrPiecewise || kind == kLrTabulated) {
+    TFRS_CHECK_ARG(table && table_len >= 1, "%s: schedule kind %d needs a device table", who, kind);
+    TFRS_CHECK_ARG(kind != kLrPiecewise || (table_len >= 2 && table_len <= 8),
+                   "%s: a piecewise schedule has 1..7 boundaries and one value more", who);
+  }
+  if (kind >= kLrExponential && kind <= kLrCosine)
+    TFRS_CHECK_ARG(params_h[1] > 0.0, "%s: decay_steps must be positive", who);
+  if (kind == kLrCosine && params_h[3] != 0.0)
+    TFRS_CHECK_ARG(params_h[5] > 0.0, "%s: warmup_steps must be positive with a warmup_target", who);
+  out->kind = kind;
+  for (int i = 0; i < 8; ++i) out->p[i] = params_h[i];
+  out->table = table;
+  out->table_len = table_len;
+  return TFRS_OK;
 }
 
 }  // namespace tfrs
@@ -119,10 +219,11 @@ extern "C" int tfrs_table_update_dense_multi(int rule, const float *hyper_h, con
   t.first_block[ntensors] = (int)blocks;
   if (blocks == 0) return TFRS_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (rule == kRuleSgd) return table_update_dense_launch(t, blocks, SgdRule{hyper_h[0]}, s);
+  // (for SGD and Ftrl a non-NULL alpha is the device floats of tfrs_lr_tick)
+  if (rule == kRuleSgd) return table_update_dense_launch(t, blocks, SgdRule{hyper_h[0], alpha}, s);
   if (rule == kRuleAdam) return table_update_dense_launch(t, blocks, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha}, s);
-  if (hyper_h[4] != 0.0f) return table_update_dense_launch(t, blocks, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]}, s);
-  return table_update_dense_launch(t, blocks, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3]}, s);
+  if (hyper_h[4] != 0.0f) return table_update_dense_launch(t, blocks, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
+  return table_update_dense_launch(t, blocks, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
 }
 
 extern "C" int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2,
@@ -131,7 +232,36 @@ extern "C" int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate,
   TFRS_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0, "adam_tick: 0 <= beta < 1");
   TFRS_CHECK_ARG(advance == 0 || advance == 1, "adam_tick: advance must be 0 or 1");
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, alpha, learning_rate, beta_1,
-                     beta_2, advance);
+                     beta_2, advance, (float *)nullptr, LrSchedule{});
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_lr_tick(int64_t *iterations, float *lr_out, int kind, const double *params_h, const float *table,
+                            int64_t table_len, int ftrl, double l2, double beta, int advance, void *stream) {
+  TFRS_CHECK_ARG(iterations && lr_out, "lr_tick: NULL pointer");
+  TFRS_CHECK_ARG(advance == 0 || advance == 1, "lr_tick: advance must be 0 or 1");
+  TFRS_CHECK_ARG(!ftrl || (l2 >= 0.0 && beta >= 0.0), "lr_tick: Ftrl regularizers must be non-negative");
+  LrSchedule s;
+  int rc = lr_schedule_check("lr_tick", kind, params_h, table, table_len, &s);
+  if (rc != TFRS_OK) return rc;
+  hipLaunchKernelGGL(lr_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, iterations, lr_out, s, ftrl, l2, beta,
+                     advance);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_adam_tick_scheduled(int64_t *step, float *alpha, float *lr_out, int kind, const double *params_h,
+                                        const float *table, int64_t table_len, double beta_1, double beta_2,
+                                        int advance, void *stream) {
+  TFRS_CHECK_ARG(step && alpha && lr_out, "adam_tick_scheduled: NULL pointer");
+  TFRS_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0, "adam_tick_scheduled: 0 <= beta < 1");
+  TFRS_CHECK_ARG(advance == 0 || advance == 1, "adam_tick_scheduled: advance must be 0 or 1");
+  LrSchedule s;
+  int rc = lr_schedule_check("adam_tick_scheduled", kind, params_h, table, table_len, &s);
+  if (rc != TFRS_OK) return rc;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, alpha, 0.0, beta_1, beta_2,
+                     advance, lr_out, s);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }

@@ -18,9 +18,15 @@ before anything is written: float32 parameters on the GPU go through the two-pas
 synchronisation and can be captured in a HIP graph.  Anything else (CPU tensors, float64) takes the same formula in
 torch ops.
 
-Deviations from the reference: ``learning_rate`` is a float (no schedules); there is no ``iterations``
-counter (a host counter would be frozen by graph replay); row-sharded tables raise ``NotImplementedError`` (their
-factor would need a min across ranks).
+``learning_rate`` is a float, a ``recommenders_amd.schedules.LearningRateSchedule`` (the reference's
+``Union[float, LearningRateSchedule]``, ``:96-113``), a 0-d float32 device tensor or a zero-argument callable returning
+one: anything but a float is read by both kernel passes from a device float that ``tfrs_lr_tick`` writes at the head of
+the step from the device counter ``iterations``, so a captured step replays the schedule (``optimizers`` module
+docstring).  With a float there is no counter (``iterations`` is ``None``; a host counter would be frozen
+by graph replay).
+
+Deviations from the reference: row-sharded tables raise ``NotImplementedError`` (their factor would need a
+min across ranks).
 """
 
 import ctypes
@@ -84,7 +90,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
              "accumulator_relative_threshold", "absolute_threshold", "epsilon", "export_clipping_factors",
              "clip_accumulator_update", "use_standard_accumulator_update")
 
-  def __init__(self, params: Iterable, learning_rate: float = 0.001, initial_accumulator_value: float = 0.1,
+  def __init__(self, params: Iterable, learning_rate=0.001, initial_accumulator_value: float = 0.1,
                variable_relative_threshold: float = 0.1, accumulator_relative_threshold: float = 0.0,
                absolute_threshold: float = 1e-7, epsilon: float = 1e-7, export_clipping_factors: bool = False,
                clip_accumulator_update: bool = False, use_standard_accumulator_update: bool = False):
@@ -93,7 +99,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     if variable_relative_threshold < 0 or accumulator_relative_threshold < 0 or absolute_threshold < 0:
       raise ValueError("the clipping thresholds must be non-negative")
     super().__init__(params, dict(
-        learning_rate=float(learning_rate), initial_accumulator_value=float(initial_accumulator_value),
+        learning_rate=learning_rate, initial_accumulator_value=float(initial_accumulator_value),
         variable_relative_threshold=float(variable_relative_threshold),
         accumulator_relative_threshold=float(accumulator_relative_threshold),
         absolute_threshold=float(absolute_threshold), epsilon=float(epsilon),
@@ -116,17 +122,20 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     self._factors = torch.ones((max(len(all_params), 1),), dtype=torch.float32, device=device)
     self.clipping_factors: List[torch.Tensor] = (
         [self._factors[i] for i in range(len(all_params))] if export_clipping_factors else [])
+    self._init_learning_rate()
 
   def get_config(self) -> Dict[str, Any]:
     group = self.param_groups[0] if self.param_groups else self.defaults
-    return {k: group[k] for k in self._CONFIG}
+    config = {k: group[k] for k in self._CONFIG}
+    config["learning_rate"] = self._config_learning_rate(config["learning_rate"])
+    return config
 
   @classmethod
   def from_config(cls, params: Iterable, config: Dict[str, Any]) -> "ClippyAdagrad":
     return cls(params, **config)
 
   def _hyper(self, group) -> Tuple[float, float, float, float, float, int]:
-    return (group["learning_rate"], group["epsilon"], group["variable_relative_threshold"],
+    return (self._step_lr(group), group["epsilon"], group["variable_relative_threshold"],
             group["accumulator_relative_threshold"], group["absolute_threshold"], _mode(group))
 
   def _on_kernel_route(self, p, acc, g) -> bool:
@@ -138,12 +147,16 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     from recommenders_amd import _lib
     n = len(items)
     vp, i64a = ctypes.c_void_p * n, ctypes.c_int64 * n
-    lr, eps, var_rel, acc_rel, abs_thr, mode = self._hyper(group)
-    _lib.check(_lib.load().tfrs_clippy_dense_multi(
-        n, vp(*[p.data_ptr() for p, _, _ in items]), vp(*[a.data_ptr() for _, a, _ in items]),
-        vp(*[g.data_ptr() for _, _, g in items]), i64a(*[p.numel() for p, _, _ in items]),
-        ctypes.c_void_p(self._factors.data_ptr() + 4 * first_slot), lr, eps, var_rel, acc_rel, abs_thr, mode,
-        _lib.current_stream()))
+    (lr, lr_dev), eps, var_rel, acc_rel, abs_thr, mode = self._hyper(group)
+    args = (n, vp(*[p.data_ptr() for p, _, _ in items]), vp(*[a.data_ptr() for _, a, _ in items]),
+            vp(*[g.data_ptr() for _, _, g in items]), i64a(*[p.numel() for p, _, _ in items]),
+            ctypes.c_void_p(self._factors.data_ptr() + 4 * first_slot), lr)
+    if lr_dev is None:
+      _lib.check(_lib.load().tfrs_clippy_dense_multi(*args, eps, var_rel, acc_rel, abs_thr, mode,
+                                                     _lib.current_stream()))
+    else:
+      _lib.check(_lib.load().tfrs_clippy_dense_multi_dlr(*args, _lib.ptr(lr_dev), eps, var_rel, acc_rel, abs_thr, mode,
+                                                         _lib.current_stream()))
     for p, _, _ in items:      # (written through raw pointers)
       torch.autograd.graph.increment_version(p)
 
@@ -158,11 +171,14 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
     rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
     ws = torch.empty((lib.tfrs_clippy_sparse_workspace_bytes(n, rowscan),), dtype=torch.uint8, device=p.device)
-    lr, eps, var_rel, acc_rel, abs_thr, mode = self._hyper(group)
-    _lib.check(lib.tfrs_clippy_sparse(
-        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, p.shape[0], _lib.ptr(p.data),
-        _lib.ptr(acc), ctypes.c_void_p(self._factors.data_ptr() + 4 * self._index[p]), lr, eps, var_rel, acc_rel,
-        abs_thr, mode, rowscan, _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+    (lr, lr_dev), eps, var_rel, acc_rel, abs_thr, mode = self._hyper(group)
+    args = (_lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, p.shape[0], _lib.ptr(p.data),
+            _lib.ptr(acc), ctypes.c_void_p(self._factors.data_ptr() + 4 * self._index[p]), lr)
+    tail = (eps, var_rel, acc_rel, abs_thr, mode, rowscan, _lib.ptr(ws), ws.numel(), _lib.current_stream())
+    if lr_dev is None:
+      _lib.check(lib.tfrs_clippy_sparse(*args, *tail))
+    else:
+      _lib.check(lib.tfrs_clippy_sparse_dlr(*args, _lib.ptr(lr_dev), *tail))
     torch.autograd.graph.increment_version(p)
 
   def _sparse_fallback(self, p, acc, ids, rows, group) -> None:
@@ -186,6 +202,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     if closure is not None:
       with torch.enable_grad():
         loss = closure()
+    self._tick()
     for group in self.param_groups:
       init = group["initial_accumulator_value"]
       for p in group["params"]:
@@ -197,7 +214,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
         if self._on_kernel_route(p, acc, rows) and ids.device == p.device:
           self._sparse_call(p, acc, ids, rows, group)
         else:
-          self._sparse_fallback(p, acc, ids.to(p.device), rows.to(p.device), group)
+          self._sparse_fallback(p, acc, ids.to(p.device), rows.to(p.device), self._host_group(group))
       run: List[tuple] = []     # dense parameters of consecutive factor slots: one call per 32
       first = 0
       for p in group["params"]:
@@ -213,7 +230,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
             first = slot
           run.append((p, acc, g.contiguous()))
           continue
-        w, a, factor = clippy_update(p.data, acc, g.to_dense() if g.is_sparse else g, group)
+        w, a, factor = clippy_update(p.data, acc, g.to_dense() if g.is_sparse else g, self._host_group(group))
         p.data.copy_(w)
         acc.copy_(a)
         self._factors[slot].copy_(factor)

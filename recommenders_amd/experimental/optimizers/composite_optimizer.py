@@ -138,19 +138,20 @@ class CompositeOptimizer:
     saved, resets = [], []
     for optimizer in self.optimizers:
       tensors = [t for st in optimizer.state.values() for t in st.values() if isinstance(t, torch.Tensor)]
-      if tensors:
-        saved.extend((t, t.detach().clone()) for t in tensors)
-      elif callable(getattr(optimizer, "reset_state_", None)):
+      # (both for a member with a learning-rate schedule: its counter exists from the constructor on, its accumulators
+      # are created by the warm-up -- those are re-initialised first, what existed is then copied back over it)
+      if callable(getattr(optimizer, "reset_state_", None)):
         resets.append(optimizer.reset_state_)
-      else:
+      elif not tensors:
         return None
+      saved.extend((t, t.detach().clone()) for t in tensors)
 
     def roll_back():
+      for fn in resets:
+        fn()
       with torch.no_grad():
         for t, v in saved:
           t.copy_(v)
-      for fn in resets:
-        fn()
 
     return roll_back
 

@@ -71,13 +71,20 @@ def scatter_add_rows(grad_out: torch.Tensor, ids: torch.Tensor, vocab: int) -> t
   return table_grad
 
 
-def _scatter_unsorted(g, flat, vocab, dst, accum, lr, eps, adagrad) -> None:
+def _scatter_unsorted(g, flat, vocab, dst, accum, lr, eps, adagrad, lr_dev=None) -> None:
   """(id, position) radix sort + segmented scatter-add / fused Adagrad in the library
-  (``tfrs_embedding_scatter_add_unsorted``); ids outside ``[0, vocab)`` are ignored."""
+  (``tfrs_embedding_scatter_add_unsorted``); ids outside ``[0, vocab)`` are ignored.  ``lr_dev``: the device float
+  the Adagrad epilogue reads its learning rate from (``optimizers`` with a schedule), in place of ``lr``."""
   lib = _lib.load()
   n = flat.numel()
   ws = torch.empty((lib.tfrs_embedding_scatter_add_workspace_bytes(n),), dtype=torch.uint8,
                    device=g.device)
+  if lr_dev is not None:
+    _lib.check(lib.tfrs_embedding_scatter_add_unsorted_dlr(
+        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, g.shape[-1], vocab,
+        _lib.ptr(dst), _lib.ptr(accum), float(lr), _lib.ptr(lr_dev), float(eps), adagrad, _lib.ptr(ws), ws.numel(),
+        _lib.current_stream()))
+    return
   _lib.check(lib.tfrs_embedding_scatter_add_unsorted(
       _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, g.shape[-1], vocab,
       _lib.ptr(dst), _lib.ptr(accum), float(lr), float(eps), adagrad, _lib.ptr(ws), ws.numel(),
@@ -85,7 +92,8 @@ def _scatter_unsorted(g, flat, vocab, dst, accum, lr, eps, adagrad) -> None:
 
 
 def adagrad_sparse_update_(table: torch.Tensor, accum: torch.Tensor, grad_out: torch.Tensor,
-                           ids: torch.Tensor, lr: float, eps: float = 1e-7, legacy: bool = False) -> None:
+                           ids: torch.Tensor, lr: float, eps: float = 1e-7, legacy: bool = False,
+                           lr_dev: Optional[torch.Tensor] = None) -> None:
   """In-place fused scatter-add + Keras Adagrad on the touched rows only
   (``models/base.py:77-78`` with ``Adagrad``, ``README.md:84``):
   g = sum of duplicate grads; acc += g*g; row -= lr * g / sqrt(acc + eps)
@@ -97,15 +105,22 @@ def adagrad_sparse_update_(table: torch.Tensor, accum: torch.Tensor, grad_out: t
     ids = ids.long()
   if _use_rowscan(table.shape[0], ids.numel(), d):
     flat = ids.reshape(-1).contiguous()
+    if lr_dev is not None:
+      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_dlr(
+          _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, flat.numel(), d,
+          table.shape[0], _lib.ptr(table), _lib.ptr(accum), float(lr), _lib.ptr(lr_dev), float(eps), mode,
+          _lib.current_stream()))
+      return
     _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan(
         _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, flat.numel(), d,
         table.shape[0], _lib.ptr(table), _lib.ptr(accum), float(lr), float(eps), mode,
         _lib.current_stream()))
     return
-  _scatter_unsorted(g, ids.reshape(-1).contiguous(), table.shape[0], table, accum, lr, eps, mode)
+  _scatter_unsorted(g, ids.reshape(-1).contiguous(), table.shape[0], table, accum, lr, eps, mode, lr_dev)
 
 
-def adagrad_sparse_update_multi_(updates, lr: float, eps: float = 1e-7, legacy: bool = False) -> None:
+def adagrad_sparse_update_multi_(updates, lr: float, eps: float = 1e-7, legacy: bool = False,
+                                 lr_dev: Optional[torch.Tensor] = None) -> None:
   """``adagrad_sparse_update_`` for several tables of one optimizer step; ``updates`` is a list of
   ``(table, accum, grad_rows, ids)``.  The small tables (row-scan path) of the step go out in
   ONE launch (``tfrs_embedding_scatter_add_rowscan_multi``): each table's update is a chain of
@@ -118,23 +133,27 @@ def adagrad_sparse_update_multi_(updates, lr: float, eps: float = 1e-7, legacy: 
     (small if _use_rowscan(table.shape[0], ids.numel(), d) else rest).append(
         (table, accum, grad_out.reshape(-1, d).contiguous(), ids.reshape(-1).contiguous()))
   for table, accum, g, ids in rest:
-    adagrad_sparse_update_(table, accum, g, ids, lr, eps, legacy)
+    adagrad_sparse_update_(table, accum, g, ids, lr, eps, legacy, lr_dev)
   for lo in range(0, len(small), 8):
     grp = small[lo:lo + 8]
     if len(grp) == 1:
       table, accum, g, ids = grp[0]
-      adagrad_sparse_update_(table, accum, g, ids, lr, eps, legacy)
+      adagrad_sparse_update_(table, accum, g, ids, lr, eps, legacy, lr_dev)
       continue
     import ctypes
     n = len(grp)
     vp, i64a, ia = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
-    _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi(
-        n, vp(*[g.data_ptr() for _, _, g, _ in grp]), vp(*[i.data_ptr() for _, _, _, i in grp]),
-        ia(*[1 if i.dtype == torch.int64 else 0 for _, _, _, i in grp]),
-        i64a(*[i.numel() for _, _, _, i in grp]), ia(*[g.shape[-1] for _, _, g, _ in grp]),
-        i64a(*[t.shape[0] for t, _, _, _ in grp]), vp(*[t.data_ptr() for t, _, _, _ in grp]),
-        vp(*[a.data_ptr() for _, a, _, _ in grp]), float(lr), float(eps), 2 if legacy else 1,
-        _lib.current_stream()))
+    args = (n, vp(*[g.data_ptr() for _, _, g, _ in grp]), vp(*[i.data_ptr() for _, _, _, i in grp]),
+            ia(*[1 if i.dtype == torch.int64 else 0 for _, _, _, i in grp]),
+            i64a(*[i.numel() for _, _, _, i in grp]), ia(*[g.shape[-1] for _, _, g, _ in grp]),
+            i64a(*[t.shape[0] for t, _, _, _ in grp]), vp(*[t.data_ptr() for t, _, _, _ in grp]),
+            vp(*[a.data_ptr() for _, a, _, _ in grp]), float(lr))
+    if lr_dev is not None:
+      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi_dlr(
+          *args, _lib.ptr(lr_dev), float(eps), 2 if legacy else 1, _lib.current_stream()))
+    else:
+      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi(
+          *args, float(eps), 2 if legacy else 1, _lib.current_stream()))
 
 
 def _emit_table_grad(ctx, grad_out):

@@ -329,11 +329,13 @@ class Model(torch.nn.Module):
             p.copy_(v)
           if member_roll_back is not None:
             member_roll_back()
-          elif had_state:
+          else:
+            # state the warm-up created lazily (accumulators beside a schedule's counter, which exists from the
+            # constructor on) goes back to its initial value; state that existed is then copied back over it
+            if callable(getattr(self.optimizer, "reset_state_", None)):
+              self.optimizer.reset_state_()
             for t, v in had_state:
               t.copy_(v)
-          else:
-            self.optimizer.reset_state_()
         for t, v in metric_before:
           t.copy_(v)
         # metric state created BY the warm-up (lazily allocated totals): back to zero, in place --
@@ -430,7 +432,8 @@ class Model(torch.nn.Module):
     """``graph=None`` (default): replay captured steps when that is known to be safe -- a ROCm device,
     no gradient exchange (a collective inside a capture is not supported here), and for training an
     optimizer whose step has no host-side state that changes from step to step: this package's
-    ``Adagrad``, ``Adam`` (its counter lives on the device), ``Ftrl``, ``SGD`` and ``experimental.optimizers.ClippyAdagrad``, a ``torch.optim`` optimizer built with
+    ``Adagrad``, ``Adam`` (its counter lives on the device), ``Ftrl``, ``SGD`` and ``experimental.optimizers.ClippyAdagrad`` -- with a
+    float learning rate or a ``recommenders_amd.schedules`` schedule, which is evaluated on the device --, a ``torch.optim`` optimizer built with
     ``capturable=True`` (a host-side step counter or learning-rate schedule would be frozen into the graph at
     capture time), or a ``CompositeOptimizer`` of such members.
     ``graph=True`` forces it, ``graph=False`` / ``TFRS_FIT_GRAPH=0`` keeps every step eager."""
@@ -469,14 +472,19 @@ class Model(torch.nn.Module):
 
   def _capture_fingerprint(self):
     """What a captured step froze at capture time, as far as it can be seen from here: the optimizer
-    object and its hyper-parameters (this package's Adagrad passes `lr` / `eps` as kernel arguments), the
+    object and its hyper-parameters (this package's Adagrad passes a float `lr` and `eps` as kernel arguments; a
+    learning-rate schedule or tensor is frozen as an object: its device floats are live, its identity is not), the
     metric objects the step updates (a `task.factorized_metrics = ...` reassignment), the sub-modules.
     Objects are kept by reference (compared with `is`), so a recycled `id()` cannot alias."""
     hyper = []
     if self.optimizer is not None:
       for group in self.optimizer.param_groups:
-        hyper.append(tuple(sorted((k, v) for k, v in group.items()
-                                  if k != "params" and isinstance(v, (int, float, bool, str, tuple, type(None))))))
+        # (a learning-rate schedule or tensor is kept by reference: replacing it, or switching between a float and a
+        # schedule, re-captures -- the tick kernel's arguments are frozen into the graph)
+        hyper.append(tuple(sorted(((k, v) for k, v in group.items()
+                                   if k != "params" and (k == "learning_rate" or
+                                                         isinstance(v, (int, float, bool, str, tuple, type(None))))),
+                                  key=lambda kv: kv[0])))
     holders = []
     for module in self.modules():
       holders.extend(getattr(module, "_factorized_metrics", None) or [])
