@@ -39,7 +39,6 @@ SOURCES = [
     "hashing.hip",
     "softmax.hip",
     "softmax16.hip",
-    "softmax_mh.hip",
     "logits_ce.hip",
     "interaction.hip",
     "gemm16.hip",

@@ -38,26 +38,39 @@ MIN_FLOAT = float(np.finfo(np.float32).min / 100.0)   # retrieval.py:26
 
 
 class _InBatchSoftmaxFn(torch.autograd.Function):
-  """loss = sum_b w_b (logsumexp_c S_bc - S_bb), gradients wrt both embedding matrices."""
+  """loss = sum_b w_b (logsumexp_c S_bc - S_bb), gradients wrt both embedding matrices.  Queries ``[B, D]``, or
+  ``[B, H, D]``: the same loss on logits ``max_h q_bh . c_c``; the gradient of a (query, candidate) pair flows to the
+  lowest head that attains the max."""
+
+  @staticmethod
+  def _entry(lib, q, c, name):
+    """The C entry point ``name`` for the rank of ``q`` and the shape arguments both families begin with."""
+    if q.dim() == 3:
+      return getattr(lib, "tfrs_inbatch_softmax_mh_" + name), (q.shape[0], q.shape[1], c.shape[0], q.shape[2])
+    return getattr(lib, "tfrs_inbatch_softmax_" + name), (q.shape[0], c.shape[0], q.shape[1])
+
+  @staticmethod
+  def _workspace(lib, q, c):
+    fn, shape = _InBatchSoftmaxFn._entry(lib, q, c, "workspace_bytes")
+    return torch.empty((fn(*shape),), dtype=torch.uint8, device=q.device)
 
   @staticmethod
   def forward(ctx, q, c, sample_weight, inv_t, log_corr, cand_ids, score_mask):
     lib = _lib.load()
     q = q.contiguous()
     c = c.contiguous()
-    nq, d = q.shape
-    nc = c.shape[0]
-    ws = torch.empty((lib.tfrs_inbatch_softmax_workspace_bytes(nq, nc, d),),
-                     dtype=torch.uint8, device=q.device)
+    nq = q.shape[0]
+    ws = _InBatchSoftmaxFn._workspace(lib, q, c)
     loss = torch.empty((), dtype=torch.float32, device=q.device)
     lse = torch.empty((nq,), dtype=torch.float32, device=q.device)
     pos = torch.empty((nq,), dtype=torch.float32, device=q.device)
-    _lib.check(lib.tfrs_inbatch_softmax_ce_fwd(
-        _lib.ptr(q), _lib.ptr(c), nq, nc, d, _lib.ptr(sample_weight), float(inv_t),
+    fwd, shape = _InBatchSoftmaxFn._entry(lib, q, c, "ce_fwd")
+    _lib.check(fwd(
+        _lib.ptr(q), _lib.ptr(c), *shape, _lib.ptr(sample_weight), float(inv_t),
         _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(loss),
         _lib.ptr(lse), _lib.ptr(pos), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-    # the workspace keeps the forward's operand images for the backward (split-fp16 path)
-    ctx.save_for_backward(q, c, sample_weight, log_corr, cand_ids, score_mask, lse, ws)
+    # 2-D: the workspace keeps the forward's operand images for the backward (split-fp16 path)
+    ctx.save_for_backward(q, c, sample_weight, log_corr, cand_ids, score_mask, lse, ws if q.dim() == 2 else None)
     ctx.inv_t = float(inv_t)
     return loss
 
@@ -65,27 +78,26 @@ class _InBatchSoftmaxFn(torch.autograd.Function):
   def backward(ctx, gloss):
     q, c, sample_weight, log_corr, cand_ids, score_mask, lse, ws = ctx.saved_tensors
     lib = _lib.load()
-    nq, d = q.shape
-    nc = c.shape[0]
     dq = torch.empty_like(q)
     dc = torch.empty_like(c)
     g = gloss.to(torch.float32).contiguous()
-    _lib.check(lib.tfrs_inbatch_softmax_ce_bwd(
-        _lib.ptr(q), _lib.ptr(c), nq, nc, d, _lib.ptr(sample_weight), ctx.inv_t,
+    reuse = ()
+    if ws is None:                                                      # multi-head: a fresh workspace
+      ws = _InBatchSoftmaxFn._workspace(lib, q, c)
+    else:
+      reuse = (0 if os.environ.get("TFRS_SOFTMAX_NO_REUSE") else 1,)
+    bwd, shape = _InBatchSoftmaxFn._entry(lib, q, c, "ce_bwd")
+    _lib.check(bwd(
+        _lib.ptr(q), _lib.ptr(c), *shape, _lib.ptr(sample_weight), ctx.inv_t,
         _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(lse),
-        _lib.ptr(g), _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(),
-        0 if os.environ.get("TFRS_SOFTMAX_NO_REUSE") else 1,
+        _lib.ptr(g), _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), *reuse,
         _lib.current_stream()))
     return dq, dc, None, None, None, None, None
 
 
-def in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
-                          sample_weight: Optional[torch.Tensor] = None,
-                          temperature: Optional[float] = None,
-                          candidate_sampling_probability: Optional[torch.Tensor] = None,
-                          candidate_ids: Optional[torch.Tensor] = None,
-                          score_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-  """Functional form of the fused default loss (retrieval.py:172-210)."""
+def _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, temperature,
+                        candidate_sampling_probability, candidate_ids, score_mask):
+  """Turns the options of the two public functions into the device tensors of the kernels and runs them."""
   dev = query_embeddings.device
   inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
   w = None if sample_weight is None else sample_weight.reshape(-1).to(dev, torch.float32).contiguous()
@@ -99,49 +111,20 @@ def in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: 
                                  candidate_embeddings.to(torch.float32), w, inv_t, corr, ids, mask)
 
 
-MAX_FUSED_HEADS = 32   # head slots of a query share one 32-row MFMA block (csrc/softmax_mh.hip)
+def in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
+                          sample_weight: Optional[torch.Tensor] = None,
+                          temperature: Optional[float] = None,
+                          candidate_sampling_probability: Optional[torch.Tensor] = None,
+                          candidate_ids: Optional[torch.Tensor] = None,
+                          score_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """Functional form of the fused default loss (retrieval.py:172-210)."""
+  if query_embeddings.dim() != 2:
+    raise ValueError(f"queries must be [B, D] (got {tuple(query_embeddings.shape)}).")
+  return _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, temperature,
+                             candidate_sampling_probability, candidate_ids, score_mask)
 
 
-class _MultiHeadSoftmaxFn(torch.autograd.Function):
-  """The same loss on logits ``max_h q_bh . c_c`` for queries ``[B, H, D]``; the gradient of a (query, candidate)
-  pair flows to the lowest head that attains the max."""
-
-  @staticmethod
-  def forward(ctx, q, c, sample_weight, inv_t, log_corr, cand_ids, score_mask):
-    lib = _lib.load()
-    q = q.contiguous()
-    c = c.contiguous()
-    nq, heads, d = q.shape
-    nc = c.shape[0]
-    ws = torch.empty((lib.tfrs_inbatch_softmax_mh_workspace_bytes(nq, heads, nc, d),),
-                     dtype=torch.uint8, device=q.device)
-    loss = torch.empty((), dtype=torch.float32, device=q.device)
-    lse = torch.empty((nq,), dtype=torch.float32, device=q.device)
-    pos = torch.empty((nq,), dtype=torch.float32, device=q.device)
-    _lib.check(lib.tfrs_inbatch_softmax_mh_ce_fwd(
-        _lib.ptr(q), _lib.ptr(c), nq, heads, nc, d, _lib.ptr(sample_weight), float(inv_t),
-        _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(loss),
-        _lib.ptr(lse), _lib.ptr(pos), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-    ctx.save_for_backward(q, c, sample_weight, log_corr, cand_ids, score_mask, lse)
-    ctx.inv_t = float(inv_t)
-    return loss
-
-  @staticmethod
-  def backward(ctx, gloss):
-    q, c, sample_weight, log_corr, cand_ids, score_mask, lse = ctx.saved_tensors
-    lib = _lib.load()
-    nq, heads, d = q.shape
-    nc = c.shape[0]
-    dq = torch.empty_like(q)
-    dc = torch.empty_like(c)
-    g = gloss.to(torch.float32).contiguous()
-    ws = torch.empty((lib.tfrs_inbatch_softmax_mh_workspace_bytes(nq, heads, nc, d),),
-                     dtype=torch.uint8, device=q.device)
-    _lib.check(lib.tfrs_inbatch_softmax_mh_ce_bwd(
-        _lib.ptr(q), _lib.ptr(c), nq, heads, nc, d, _lib.ptr(sample_weight), ctx.inv_t,
-        _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(lse),
-        _lib.ptr(g), _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-    return dq, dc, None, None, None, None, None
+MAX_FUSED_HEADS = 32   # head slots of a query share one 32-row MFMA block (csrc/softmax.hip)
 
 
 def multi_head_in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
@@ -160,17 +143,8 @@ def multi_head_in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_e
     raise ValueError(f"multi_head_in_batch_softmax_loss: {heads} heads outside [1, {MAX_FUSED_HEADS}]")
   if d > 128:
     raise ValueError(f"multi_head_in_batch_softmax_loss: embedding dim {d} above 128")
-  dev = query_embeddings.device
-  inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
-  w = None if sample_weight is None else sample_weight.reshape(-1).to(dev, torch.float32).contiguous()
-  corr = None
-  if candidate_sampling_probability is not None:                      # loss.py:157-158
-    corr = torch.log(torch.clamp(candidate_sampling_probability.to(dev, torch.float32),
-                                 1e-6, 1.0)).contiguous()
-  ids = None if candidate_ids is None else candidate_ids.reshape(-1).to(dev).long().contiguous()
-  mask = None if score_mask is None else score_mask.to(dev).to(torch.uint8).contiguous()
-  return _MultiHeadSoftmaxFn.apply(query_embeddings.to(torch.float32),
-                                   candidate_embeddings.to(torch.float32), w, inv_t, corr, ids, mask)
+  return _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, temperature,
+                             candidate_sampling_probability, candidate_ids, score_mask)
 
 
 def hard_negative_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,

@@ -122,7 +122,8 @@ def test_new_symbols_are_in_the_header_the_library_and_the_binding(lib):
     assert re.search(r"\b%s\(" % name, header), name
     assert hasattr(lib, name), name
     assert name in _lib.SIGNATURES, name
-  assert "softmax_mh.hip" in csrc_build.SOURCES
+  assert "softmax.hip" in csrc_build.SOURCES                     # the multi-head kernels live in the merged file
+  assert not os.path.exists(os.path.join(os.path.dirname(csrc_build.__file__), "softmax_mh.hip"))
 
 
 _BUF = ctypes.create_string_buffer(64)            # a non-NULL host address: never dereferenced by a refused call
@@ -224,25 +225,32 @@ def _asm(src_name):
   return _ASM[src_name]
 
 
+# the kernels of softmax.hip by their last template argument, MH (mangled: Lb1E = true, Lb0E = false)
+_SOFTMAX_KERNEL = r"softmax_%s_kernelI\w*Lb%dEEEv"
+
+
 def test_multi_head_softmax_kernels_pass_the_mfma_hazard_checker():
   import importlib.util
   spec = importlib.util.spec_from_file_location("check_mfma_hazards",
                                                 os.path.join(ROOT, "tools", "check_mfma_hazards.py"))
   mod = importlib.util.module_from_spec(spec)
   spec.loader.exec_module(mod)
-  res = mod.check(_asm("softmax_mh.hip"))
-  assert sum("softmax_mh_fwd_kernel" in name for name in res) == 10       # 5 padded dims x {plain, options}
-  assert sum("softmax_mh_bwd_kernel" in name for name in res) == 20       # ... x {dq, dc}
+  res = mod.check(_asm("softmax.hip"))
+  for mh in (1, 0):
+    assert sum(bool(re.search(_SOFTMAX_KERNEL % ("fwd", mh), name)) for name in res) == 10   # 5 padded dims x {plain, options}
+    assert sum(bool(re.search(_SOFTMAX_KERNEL % ("bwd", mh), name)) for name in res) == 20   # ... x {dq, dc}
   assert not {k: v[:3] for k, v in res.items() if v}
 
 
-@pytest.mark.parametrize("src_name,pattern,count", [("softmax_mh.hip", "softmax_mh", 30),
-                                                    ("topk_merge_heads.hip", "merge_heads", 1)])
+@pytest.mark.parametrize("src_name,pattern,count", [
+    pytest.param("softmax.hip", _SOFTMAX_KERNEL % ("(fwd|bwd)", 1), 30, id="softmax.hip-multi_head-30"),
+    pytest.param("softmax.hip", _SOFTMAX_KERNEL % ("(fwd|bwd)", 0), 30, id="softmax.hip-single_head-30"),
+    ("topk_merge_heads.hip", "merge_heads", 1)])
 def test_new_kernels_use_no_scratch(src_name, pattern, count):
   found = 0
   for block in _asm(src_name).split("- .agpr_count:")[1:]:
     name = re.search(r"\.name:\s+(\S+)", block).group(1)
-    if pattern not in name:
+    if not re.search(pattern, name):
       continue
     found += 1
     assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0, name
