@@ -608,6 +608,16 @@ int tfrs_inbatch_softmax_mh_ce_bwd(const float *q, const float *c, int64_t nq, i
                                    const float *log_q_correction, const int64_t *cand_ids,
                                    const uint8_t *score_mask, const float *lse, const float *gloss, float *dq,
                                    float *dc, void *workspace, size_t workspace_bytes, void *stream);
+/* The split geometry of the in-batch softmax kernels under the options in force (TFRS_SOFTMAX_WAVES, _WGS, _WGS_BWD,
+ * _NW: all read per call).  Host only, no device call; the launches use exactly these plans.  A side's streamed rows
+ * are cut into nsplit splits of split_len rows (a multiple of 32; the last split may be shorter).
+ *   _plan_f32 (f32-MFMA kernels, 1 <= heads <= 32): out[4] = {nsplit, split_len} of the forward / dq (streams the nc
+ *             candidates), then of dc (streams the nq * Hp flat head slots, Hp = heads rounded up to a power of two)
+ *   _plan_f16 (split-fp16 kernels): out[6] = {nsplit, split_len} of the forward, of dq (both stream candidates) and
+ *             of dc (streams queries)
+ * nq >= 1, nc >= nq, out != NULL, else TFRS_EINVAL. */
+int tfrs_inbatch_softmax_plan_f32(int64_t nq, int heads, int64_t nc, int64_t *out);
+int tfrs_inbatch_softmax_plan_f16(int64_t nq, int64_t nc, int64_t *out);
 
 /* Multi-head exact top-K (BruteForce on queries [nq, heads, d]): scores / rows [nq, heads, k_in] are the top-k_in
  * lists of the nq * heads flat (query, head) rows (descending; row < 0 = empty).  Writes, per query, the top-k_out

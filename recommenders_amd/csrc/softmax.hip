@@ -255,7 +255,9 @@ __global__ void __launch_bounds__(256) softmax_finalize_kernel(const SoftmaxArgs
     out_lse[row] = lse;
     out_pos[row] = pos;
     const float w = a.w ? a.w[row] : 1.0f;
-    local = (double)w * ((double)lse - (double)pos);
+    // (mm - pos) + log(ll), not lse - pos: for a row whose score_mask is all False mm and pos are both kMinFloat, whose
+    // ulp (2.5e29) swallows log(ll) in lse -- the difference first is exact there and the row's loss is log(nc)
+    local = (double)w * ((double)(mm - pos) + (double)logf(ll));
   }
   red[threadIdx.x] = local;
   __syncthreads();
@@ -481,11 +483,15 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const float *parti
 
 // How many waves share one block of 32 owned rows (`row_blocks` of them) that streams `tiles`
 // 32-row tiles of the other side: the number of splits and their length in rows.
-static void softmax_plan_blocks(int64_t row_blocks, int64_t tiles, int *nsplit, int64_t *split_len) {
-  static const int64_t target_waves = [] {
-    const char *v = option("TFRS_SOFTMAX_WAVES");
-    return (v && *v) ? (int64_t)atoll(v) : (int64_t)2048;  // ~2 waves per SIMD on 256 CUs
-  }();
+// The planner's target (TFRS_SOFTMAX_WAVES), resolved once per entry-point call -- read per call: tests switch it --
+// and handed down to every plan of that call.
+static int64_t resolve_target_waves() {
+  const char *v = option("TFRS_SOFTMAX_WAVES");
+  return (v && *v) ? (int64_t)atoll(v) : (int64_t)2048;  // ~2 waves per SIMD on 256 CUs
+}
+
+static void softmax_plan_blocks(int64_t target_waves, int64_t row_blocks, int64_t tiles, int *nsplit,
+                                int64_t *split_len) {
   int64_t want = (target_waves + row_blocks - 1) / row_blocks;
   if (want > tiles) want = tiles;
   if (want < 1) want = 1;
@@ -501,13 +507,13 @@ static int log2_padded_heads(int heads) {
 }
 
 // splits of the forward / dq kernels (waves own query blocks) and of the dc kernel (waves own candidates)
-static void plan_queries(int64_t nq, int lhp, int64_t nc, int *nsplit, int64_t *split_len) {
+static void plan_queries(int64_t target_waves, int64_t nq, int lhp, int64_t nc, int *nsplit, int64_t *split_len) {
   const int qw = 32 >> lhp;
-  softmax_plan_blocks((nq + qw - 1) / qw, (nc + 31) / 32, nsplit, split_len);
+  softmax_plan_blocks(target_waves, (nq + qw - 1) / qw, (nc + 31) / 32, nsplit, split_len);
 }
-static void plan_candidates(int64_t nq, int lhp, int64_t nc, int *nsplit, int64_t *split_len) {
+static void plan_candidates(int64_t target_waves, int64_t nq, int lhp, int64_t nc, int *nsplit, int64_t *split_len) {
   const int qw = 32 >> lhp;
-  softmax_plan_blocks((nc + 31) / 32, (nq + qw - 1) / qw, nsplit, split_len);
+  softmax_plan_blocks(target_waves, (nc + 31) / 32, (nq + qw - 1) / qw, nsplit, split_len);
 }
 
 // softmax_finalize_kernel on the [nsplit, nq] partial (max, sum) pairs and the positives of `a`
@@ -564,8 +570,9 @@ static size_t f32_workspace_bytes(int64_t nq, int heads, int64_t nc, int d) {
   const int lhp = log2_padded_heads(heads);
   int nsq, nsc;
   int64_t len;
-  plan_queries(nq, lhp, nc, &nsq, &len);
-  plan_candidates(nq, lhp, nc, &nsc, &len);
+  const int64_t target = resolve_target_waves();
+  plan_queries(target, nq, lhp, nc, &nsq, &len);
+  plan_candidates(target, nq, lhp, nc, &nsc, &len);
   const size_t fwd = 2 * al((size_t)nsq * nq * 4) + al((size_t)nq * 4) +
                      al((size_t)((nq + 255) / 256) * 8) + al(4);  // + finalize partials, ticket
   const size_t bwd = al((size_t)nsq * nq * heads * d * 4) + al((size_t)nsc * nc * d * 4);
@@ -586,7 +593,7 @@ static SoftmaxArgs make_args(const float *q, const float *c, int64_t nq, int hea
 template <bool MH>
 static int run_fwd(SoftmaxArgs a, float *out_loss, float *out_lse, float *out_pos, void *workspace,
                    hipStream_t s) {
-  plan_queries(a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
+  plan_queries(resolve_target_waves(), a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
   char *p = static_cast<char *>(workspace);
   a.pm = reinterpret_cast<float *>(p); p += al((size_t)a.nsplit * a.nq * 4);
   a.pl = reinterpret_cast<float *>(p); p += al((size_t)a.nsplit * a.nq * 4);
@@ -603,9 +610,10 @@ static int run_fwd(SoftmaxArgs a, float *out_loss, float *out_lse, float *out_po
 template <bool MH>
 static int run_bwd(SoftmaxArgs a, float *dq, float *dc, void *workspace, hipStream_t s) {
   char *p = static_cast<char *>(workspace);
+  const int64_t target = resolve_target_waves();
 
   // dq: waves own query blocks, stream candidates
-  plan_queries(a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
+  plan_queries(target, a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
   a.partial = reinterpret_cast<float *>(p);
   const int64_t nqd = a.nq * a.heads * a.d;
   for_padded_dim(a.d, [&](auto dp) { launch_bwd<decltype(dp)::value, true, MH>(a, s); });
@@ -615,7 +623,7 @@ static int run_bwd(SoftmaxArgs a, float *dq, float *dc, void *workspace, hipStre
 
   // dc: waves own candidates, stream the flat (query, head) rows
   p += al((size_t)a.nsplit * nqd * 4);
-  plan_candidates(a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
+  plan_candidates(target, a.nq, a.lhp, a.nc, &a.nsplit, &a.split_len);
   a.partial = reinterpret_cast<float *>(p);
   for_padded_dim(a.d, [&](auto dp) { launch_bwd<decltype(dp)::value, false, MH>(a, s); });
   TFRS_LAUNCH_CHECK();
@@ -707,6 +715,20 @@ extern "C" int tfrs_inbatch_softmax_ce_bwd(const float *q, const float *c, int64
                             score_mask);
   a.lse = lse; a.gloss = gloss;
   return run_bwd<false>(a, dq, dc, workspace, (hipStream_t)stream);
+}
+
+// The split geometry of the f32 kernels under the options in force (host only, no device call): nsplit and split_len
+// of plan_queries (forward, dq) and of plan_candidates (dc), from the planners the launches above use.
+extern "C" int tfrs_inbatch_softmax_plan_f32(int64_t nq, int heads, int64_t nc, int64_t *out) {
+  TFRS_CHECK_ARG(nq >= 1 && nc >= nq && heads >= 1 && heads <= 32 && out, "inbatch_softmax_plan_f32: bad argument");
+  const int lhp = log2_padded_heads(heads);
+  const int64_t target = resolve_target_waves();
+  int ns;
+  plan_queries(target, nq, lhp, nc, &ns, &out[1]);
+  out[0] = ns;
+  plan_candidates(target, nq, lhp, nc, &ns, &out[3]);
+  out[2] = ns;
+  return TFRS_OK;
 }
 
 // ---- multi-head queries: the MH = true kernels for every heads in 1 .. 32

@@ -759,11 +759,29 @@ __global__ void __launch_bounds__(256) sm16_reduce2_kernel(const float *pa, int 
 // ---- host side ----------------------------------------------------------------------------
 static inline size_t al16(size_t x) { return (x + 255) / 256 * 256; }
 static inline int64_t pad128(int64_t n) { return (n + 255) / 256 * 256; }   // records cover whole 256-row blocks
-// waves per workgroup for a side with n_rows owned rows
-static inline int nw_of(int64_t n_rows) {
-  const char *v = option("TFRS_SOFTMAX_NW");   // read per call: tests switch it
+// The launch geometry's options (TFRS_SOFTMAX_NW, _WGS, _WGS_BWD), resolved ONCE per entry-point call -- read per
+// call: tests switch them -- and handed down to every plan of that call.
+struct Opt16 {
+  int nw;                 // forced waves per workgroup (4 / 8), 0 = by size
+  int64_t fwd, bwd;       // workgroup targets of the forward / of each side of the backward
+};
+static Opt16 resolve_opt16() {
+  Opt16 o;
+  const char *v = option("TFRS_SOFTMAX_NW");
   const int forced = (v && *v) ? atoi(v) : 0;
-  if (forced == 4 || forced == 8) return forced;
+  o.nw = (forced == 4 || forced == 8) ? forced : 0;
+  v = option("TFRS_SOFTMAX_WGS");
+  o.fwd = (v && *v) ? (int64_t)atoll(v) : (int64_t)512;   // 2 workgroups per CU
+  // The backward's two sides share one launch, and LDS holds two of its workgroups per CU: 256 per side are ONE
+  // round of resident workgroups (512 per side ran as two rounds, each paying the ~3 us prologue -- first touch of the
+  // records, owned rows -- and wrote twice the partial gradients: 4096 x 4096 x 64, bwd + reduce 45.0 -> 41.9 us)
+  v = option("TFRS_SOFTMAX_WGS_BWD");
+  o.bwd = (v && *v) ? (int64_t)atoll(v) : (int64_t)256;
+  return o;
+}
+// waves per workgroup for a side with n_rows owned rows
+static inline int nw_of(const Opt16 &opt, int64_t n_rows) {
+  if (opt.nw) return opt.nw;
   return n_rows >= 16384 ? 8 : 4;
 }
 static inline int dp_of(int d) { return d <= 32 ? 32 : (d <= 64 ? 64 : 128); }
@@ -771,22 +789,12 @@ static inline size_t rec_bytes(int dp) {
   return dp == 32 ? Rec16<32>::kBytes : (dp == 64 ? Rec16<64>::kBytes : Rec16<128>::kBytes);
 }
 
-static void plan16(int64_t n_rows, int64_t n_stream, int *nsplit, int64_t *split_len, bool backward = false) {
-  const int64_t per_wg = nw_of(n_rows) * 32;
+static void plan16(const Opt16 &opt, int64_t n_rows, int64_t n_stream, int *nsplit, int64_t *split_len,
+                   bool backward = false) {
+  const int64_t per_wg = nw_of(opt, n_rows) * 32;
   const int64_t row_blocks = (n_rows + per_wg - 1) / per_wg;
   const int64_t tiles = (n_stream + 31) / 32;
-  static const int64_t target_fwd = [] {
-    const char *v = option("TFRS_SOFTMAX_WGS");
-    return (v && *v) ? (int64_t)atoll(v) : (int64_t)512;   // 2 workgroups per CU
-  }();
-  // The backward's two sides share one launch, and LDS holds two of its workgroups per CU: 256 per side are ONE
-  // round of resident workgroups (512 per side ran as two rounds, each paying the ~3 us prologue -- first touch of the
-  // records, owned rows -- and wrote twice the partial gradients: 4096 x 4096 x 64, bwd + reduce 45.0 -> 41.9 us)
-  static const int64_t target_bwd = [] {
-    const char *v = option("TFRS_SOFTMAX_WGS_BWD");
-    return (v && *v) ? (int64_t)atoll(v) : (int64_t)256;
-  }();
-  const int64_t target = backward ? target_bwd : target_fwd;
+  const int64_t target = backward ? opt.bwd : opt.fwd;
   int64_t want = (target + row_blocks - 1) / row_blocks;
   if (want > tiles) want = tiles;
   if (want < 1) want = 1;
@@ -799,7 +807,7 @@ struct Layout16 {
   size_t header, q_rec, q_bmax, c_rec, c_bmax, scratch, total;
 };
 
-static Layout16 layout16(int64_t nq, int64_t nc, int d) {
+static Layout16 layout16(const Opt16 &opt, int64_t nq, int64_t nc, int d) {
   const int dp = dp_of(d);
   const int64_t nqp = pad128(nq), ncp = pad128(nc);
   Layout16 L;
@@ -812,9 +820,9 @@ static Layout16 layout16(int64_t nq, int64_t nc, int d) {
   L.scratch = o;
   int nsf, nsq, nsc;
   int64_t len;
-  plan16(nq, nc, &nsf, &len);
-  plan16(nq, nc, &nsq, &len, true);
-  plan16(nc, nq, &nsc, &len, true);
+  plan16(opt, nq, nc, &nsf, &len);
+  plan16(opt, nq, nc, &nsq, &len, true);
+  plan16(opt, nc, nq, &nsc, &len, true);
   const size_t fwd = 2 * al16((size_t)nsf * nq * 4) + al16((size_t)nq * 4) +
                      al16((size_t)((nq + 63) / 64) * 8);
   const size_t bwd = al16((size_t)nsq * nq * d * 4) + al16((size_t)nsc * nc * d * 4);
@@ -822,7 +830,7 @@ static Layout16 layout16(int64_t nq, int64_t nc, int d) {
   return L;
 }
 
-size_t softmax16_workspace_bytes(int64_t nq, int64_t nc, int d) { return layout16(nq, nc, d).total; }
+size_t softmax16_workspace_bytes(int64_t nq, int64_t nc, int d) { return layout16(resolve_opt16(), nq, nc, d).total; }
 
 static void fill_sides(Sm16Args *a, char *ws, const Layout16 &L, int64_t nq, int64_t nc) {
   a->q = {ws + L.q_rec, reinterpret_cast<const uint32_t *>(ws + L.q_bmax), nq, pad128(nq)};
@@ -846,20 +854,21 @@ template <int DP>
 static int fwd16(const float *q, const float *c, int64_t nq, int64_t nc, int d, const float *w,
                  float inv_t, float *out_loss, float *out_lse, float *out_pos, char *ws,
                  hipStream_t s) {
-  const Layout16 L = layout16(nq, nc, d);
+  const Opt16 opt = resolve_opt16();
+  const Layout16 L = layout16(opt, nq, nc, d);
   int rc = prep16<DP>(q, c, nq, nc, d, w, ws, L, s);
   if (rc != TFRS_OK) return rc;
   Sm16Args a = {};
   fill_sides(&a, ws, L, nq, nc);
   a.d = d; a.w = w; a.inv_t = inv_t;
-  plan16(nq, nc, &a.nsplit, &a.split_len);
+  plan16(opt, nq, nc, &a.nsplit, &a.split_len);
   char *p = ws + L.scratch;
   a.pm = reinterpret_cast<float *>(p); p += al16((size_t)a.nsplit * nq * 4);
   a.pl = reinterpret_cast<float *>(p); p += al16((size_t)a.nsplit * nq * 4);
   a.ppos = reinterpret_cast<float *>(p); p += al16((size_t)nq * 4);
   double *block_part = reinterpret_cast<double *>(p);
   uint32_t *ticket = reinterpret_cast<uint32_t *>(ws + L.header);
-  if (nw_of(nq) == 8) {
+  if (nw_of(opt, nq) == 8) {
     hipLaunchKernelGGL((sm16_fwd_kernel<DP, 8>), dim3((unsigned)(((nq + 255) / 256) * a.nsplit)),
                        dim3(512), 0, s, a);
   } else {
@@ -878,7 +887,8 @@ template <int DP>
 static int bwd16(const float *q, const float *c, int64_t nq, int64_t nc, int d, const float *w,
                  float inv_t, const float *lse, const float *gloss, float *dq, float *dc, char *ws,
                  int reuse, hipStream_t s) {
-  const Layout16 L = layout16(nq, nc, d);
+  const Opt16 opt = resolve_opt16();
+  const Layout16 L = layout16(opt, nq, nc, d);
   if (!reuse) {
     int rc = prep16<DP>(q, c, nq, nc, d, w, ws, L, s);
     if (rc != TFRS_OK) return rc;
@@ -892,17 +902,17 @@ static int bwd16(const float *q, const float *c, int64_t nq, int64_t nc, int d, 
   char *p = ws + L.scratch;
 
   Sm16Args aq = a, ac = a;
-  plan16(nq, nc, &aq.nsplit, &aq.split_len, true);
+  plan16(opt, nq, nc, &aq.nsplit, &aq.split_len, true);
   const int nsq = aq.nsplit;
   float *part_q = nsq == 1 ? dq : reinterpret_cast<float *>(p);
   aq.partial = part_q;
   p += al16((size_t)nsq * nq * d * 4);
-  plan16(nc, nq, &ac.nsplit, &ac.split_len, true);
+  plan16(opt, nc, nq, &ac.nsplit, &ac.split_len, true);
   const int nsc = ac.nsplit;
   float *part_c = nsc == 1 ? dc : reinterpret_cast<float *>(p);
   ac.partial = part_c;
   // both directions in one launch (a second launch only if the two sides differ in workgroup size)
-  const int nwq = nw_of(nq), nwc = nw_of(nc);
+  const int nwq = nw_of(opt, nq), nwc = nw_of(opt, nc);
   const int qb = (int)(((nq + nwq * 32 - 1) / (nwq * 32)) * nsq);
   const int cb = (int)(((nc + nwc * 32 - 1) / (nwc * 32)) * nsc);
   if (nwq == nwc) {
@@ -954,3 +964,18 @@ int softmax16_backward(const float *q, const float *c, int64_t nq, int64_t nc, i
 }
 
 }  // namespace tfrs
+
+// The split geometry of the split-fp16 kernels under the options in force (host only, no device call): nsplit and
+// split_len of the forward, of the backward's dq side and of its dc side, from the planner the launches above use.
+extern "C" int tfrs_inbatch_softmax_plan_f16(int64_t nq, int64_t nc, int64_t *out) {
+  TFRS_CHECK_ARG(nq >= 1 && nc >= nq && out, "inbatch_softmax_plan_f16: bad argument");
+  const tfrs::Opt16 opt = tfrs::resolve_opt16();
+  int ns;
+  tfrs::plan16(opt, nq, nc, &ns, &out[1]);
+  out[0] = ns;
+  tfrs::plan16(opt, nq, nc, &ns, &out[3], true);
+  out[2] = ns;
+  tfrs::plan16(opt, nc, nq, &ns, &out[5], true);
+  out[4] = ns;
+  return TFRS_OK;
+}

@@ -18,6 +18,7 @@ import pytest
 from oracle import topk as o_topk
 from tests import multihead_restatement as mh
 from tests.conftest import float_gate, load_golden
+from tests.softmax_handbuilt import entry_point_outputs as _entry_point_outputs
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -218,34 +219,6 @@ ROUTE_SHAPES = ((5, 5, 8),          # one partial tile
                 (64, 97, 128))      # DP = 128, two full row blocks
 
 
-def _entry_point_outputs(q, c, kw, multi_head):
-  """(loss, lse, dq, dc) of one forward + backward through the C entry points: the multi-head ones on ``q[:, None, :]``
-  (the MH = true kernels at one head) or the 2-D ones on ``q`` (the MH = false kernels under TFRS_SOFTMAX_MODE=f32)."""
-  from recommenders_amd import _lib
-  lib = _lib.load()
-  (nq, d), nc = q.shape, c.shape[0]
-  tq, tc = _t(q), _t(c)
-  w = _t(kw["sample_weight"]) if "sample_weight" in kw else None
-  corr = (torch.log(torch.clamp(_t(kw["candidate_sampling_probability"]), 1e-6, 1.0))
-          if "candidate_sampling_probability" in kw else None)
-  ids = _t(kw["candidate_ids"]).long() if "candidate_ids" in kw else None
-  mask = _t(kw["score_mask"]).to(torch.uint8).contiguous() if "score_mask" in kw else None
-  options = (_lib.ptr(w), 1.0 / kw.get("temperature", 1.0), _lib.ptr(corr), _lib.ptr(ids), _lib.ptr(mask))
-  shape = (nq, 1, nc, d) if multi_head else (nq, nc, d)
-  name = "tfrs_inbatch_softmax_mh_" if multi_head else "tfrs_inbatch_softmax_"
-  ws = torch.empty((getattr(lib, name + "workspace_bytes")(*shape),), dtype=torch.uint8, device=tq.device)
-  loss, one = torch.empty((), device=tq.device), torch.ones((), device=tq.device)
-  lse, pos = torch.empty((nq,), device=tq.device), torch.empty((nq,), device=tq.device)
-  dq, dc = torch.empty_like(tq), torch.empty_like(tc)
-  stream = _lib.current_stream()
-  _lib.check(getattr(lib, name + "ce_fwd")(_lib.ptr(tq), _lib.ptr(tc), *shape, *options, _lib.ptr(loss), _lib.ptr(lse),
-                                           _lib.ptr(pos), _lib.ptr(ws), ws.numel(), stream))
-  _lib.check(getattr(lib, name + "ce_bwd")(_lib.ptr(tq), _lib.ptr(tc), *shape, *options, _lib.ptr(lse), _lib.ptr(one),
-                                           _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(),
-                                           *(() if multi_head else (0,)), stream))
-  return tuple(_np(x) for x in (loss, lse, dq, dc))
-
-
 def _routes_at(shape):
   """{variant: (multi-head outputs, 2-D outputs)} for random normal inputs of ``shape``, plain and with every option."""
   nq, nc, d = shape
@@ -274,16 +247,15 @@ def test_one_head_through_the_multi_head_entry_points_is_the_2d_f32_route_bit_fo
 
 
 def test_one_head_equals_the_2d_f32_route_with_more_splits_asked_for():
-  """The same at (33, 70, 20) under TFRS_SOFTMAX_WAVES=4096.  The split planner reads that option once per process, so
-  the comparison runs in a fresh child."""
-  import os
-  import subprocess
-  import sys
-  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-  code = "from tests import test_multihead_gpu as t; t._assert_routes_identical((33, 70, 20)); print('routes identical')"
-  res = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, TFRS_SOFTMAX_WAVES="4096", TFRS_SOFTMAX_MODE="f32"))
-  assert res.returncode == 0 and "routes identical" in res.stdout, res.stdout + res.stderr
+  """The same at (33, 70, 20) under TFRS_SOFTMAX_WAVES=4096 (the split planner reads the option on every call)."""
+  from recommenders_amd import _lib
+  try:
+    _lib.set_option("TFRS_SOFTMAX_WAVES", "4096")
+    _lib.set_option("TFRS_SOFTMAX_MODE", "f32")
+    _assert_routes_identical((33, 70, 20))
+  finally:
+    _lib.set_option("TFRS_SOFTMAX_WAVES", None)
+    _lib.set_option("TFRS_SOFTMAX_MODE", None)
 
 
 # ------------------------------------------------------------------------------------------ Retrieval routing
