@@ -451,6 +451,23 @@ int tfrs_table_update_dense_multi(int rule, const float *hyper_h, const float *a
                                   const float *const *grads_h, const int64_t *n_h, void *stream);
 int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2, int advance,
                    void *stream);
+/* optimizers.RowWiseAdagrad: Adagrad with ONE accumulator scalar per row of a [vocab, d] table (accum: float32 [vocab]),
+ * f32 in the written order, no contraction.  With G the row's summed gradient:
+ *   s = (sum_j G_j * G_j) / d;  acc' = acc + s;  den = sqrt(acc' + eps)  (mode 1)  or  sqrt(acc') + eps  (mode 2);
+ *   scale = lr / den  (one division per row);  w_j' = w_j - scale * G_j
+ * The order of the d additions is fixed (csrc/table_rules.h), so a call is bit-reproducible.
+ * _sparse: the looked-up rows, from UNSORTED ids (int32 / int64) and grad_out[n, d]; duplicates are summed first, in the
+ * order of tfrs_table_update_sparse (the same bits); ids outside [0, vocab) are ignored; untouched rows are not written.
+ * rowscan != 0: the sort-free row scan (d <= 256), else radix sort + one lane group per run, with workspace from
+ * tfrs_table_update_workspace_bytes(n, rowscan).  n == 0: nothing is written.
+ * _dense: every row of param[rows, d] from grad[rows, d]; a row whose gradient is all zero keeps its bits.
+ * lr_dev: NULL (lr is taken by value), or the device float of tfrs_lr_tick, read once at kernel entry.
+ * Every argument check comes before any device call. */
+int tfrs_rowwise_adagrad_sparse(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d, int64_t vocab,
+                                float *table, float *accum, float lr, const float *lr_dev, float eps, int mode,
+                                int rowscan, void *workspace, size_t workspace_bytes, void *stream);
+int tfrs_rowwise_adagrad_dense(float *param, float *accum, const float *grad, int64_t rows, int d, float lr,
+                               const float *lr_dev, float eps, int mode, void *stream);
 /* Learning-rate schedules on the device (recommenders_amd/schedules.py): the learning rate of a step is a DEVICE float
  * that a one-thread kernel at the head of the step writes from a DEVICE counter, so a captured step replays the whole
  * schedule.  A schedule is a kind, a HOST array of 8 doubles and (kinds 0, 5, 6) a DEVICE f32 table of table_len entries;

@@ -95,6 +95,9 @@ SIGNATURES = {
     "tfrs_table_update_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "tfrs_table_update_sparse": (c_int, [c_int, P, P, P, P, c_int, c_i64, c_int, c_i64, P, P, P, c_int, P, c_size_t, P]),
     "tfrs_table_update_dense_multi": (c_int, [c_int, P, P, c_int, P, P, P, P, P, P]),
+    "tfrs_rowwise_adagrad_sparse": (c_int, [P, P, c_int, c_i64, c_int, c_i64, P, P, c_float, P, c_float, c_int, c_int, P,
+                                            c_size_t, P]),
+    "tfrs_rowwise_adagrad_dense": (c_int, [P, P, P, c_i64, c_int, c_float, P, c_float, c_int, P]),
     "tfrs_adam_tick": (c_int, [P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, P]),
     "tfrs_copy_multi": (c_int, [c_int, P, P, P, P]),
     "tfrs_lr_tick": (c_int, [P, P, c_int, P, P, c_i64, c_int, ctypes.c_double, ctypes.c_double, c_int, P]),

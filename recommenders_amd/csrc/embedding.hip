@@ -329,7 +329,9 @@ constexpr int kRowscanHitCap = 128;
 // (clippy_rowscan_kernel below: the same scan and the same occurrence-order sums, another epilogue).
 // RULE: void, or an update rule of table_rules.h (table_update_rowscan_kernel below): the touched rows of dst, accum (the
 // rule's first slot) and slot1 go through rule->apply, untouched rows are not written.
-template <typename IdT, int NS, int CLIPPY = 0, typename RULE = void>
+// ROWWISE: 1 = optimizers.RowWiseAdagrad (rowwise_adagrad_rowscan_kernel at the end of this file): accum is ONE float per
+// row, `adagrad` the denominator's mode; the touched rows go through the row-wise functions of table_rules.h.
+template <typename IdT, int NS, int CLIPPY = 0, typename RULE = void, int ROWWISE = 0>
 __device__ __forceinline__ void scatter_rowscan_body_ns(
     const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d,
     int64_t vocab, float *__restrict__ dst, float *__restrict__ accum, float lr, float eps,
@@ -412,6 +414,30 @@ __device__ __forceinline__ void scatter_rowscan_body_ns(
       __builtin_amdgcn_wave_barrier();
     }
     flush();
+  }
+  if constexpr (ROWWISE != 0) {
+    if (row_ok && touched) {   // wave-uniform
+      float pv[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) pv[s] = dst[v * d + fo[s]];
+      const float a_old = lane == 0 ? accum[v] : 0.0f;
+      float partial = 0.0f;     // features lane, lane + 64, ... in ascending order, then the butterfly over the wave
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+        if (fok[s]) partial = rowwise_sq_add(partial, g[s]);
+      const float sum_sq = rowwise_group_sum(partial, 64);
+      float scale = 0.0f;
+      if (lane == 0) {
+        const float a_new = rowwise_accumulate(a_old, sum_sq, d);
+        accum[v] = a_new;
+        scale = rowwise_scale(a_new, lr, eps, adagrad);
+      }
+      scale = __shfl(scale, 0);
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+        if (fok[s]) dst[v * d + fo[s]] = rowwise_step(pv[s], scale, g[s]);
+    }
+    return;
   }
   if constexpr (!std::is_void<RULE>::value) {
     if (row_ok && touched) {   // wave-uniform
@@ -1729,4 +1755,165 @@ extern "C" int tfrs_table_update_sparse(int rule, const float *hyper_h, const fl
   if (rule == kRuleAdam) return table_update_sparse_launch(a, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha});
   if (hyper_h[4] != 0.0f) return table_update_sparse_launch(a, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha});
   return table_update_sparse_launch(a, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha});
+}
+
+// ---- optimizers.RowWiseAdagrad on the looked-up rows of a table (table_rules.h: one accumulator scalar per row) ------
+// The same sort and the same piece-wise sums of long runs as every other sparse update (sort_id_positions,
+// scatter_add_pieces_kernel: the summed gradient is bit for bit theirs), but the rule needs the whole row's sum of
+// squares before any element moves, so the thread layout differs from table_update_sorted_kernel: every sorted
+// POSITION owns a group of 2^group_shift lanes (the power of two >= d / VEC, at most 64: a group never straddles a
+// wave), only the groups of run starts work, and rowwise_adagrad_row does the rest -- a lane keeps its chunk of the
+// summed gradient in registers, the group reduces the squares across lanes, one lane reads and writes acc[id] and
+// divides, all lanes apply the scale to the G they still hold.  Rows wider than one chunk per lane (REREAD: d > 256
+// on the float4 path, d > 64 on the scalar one) read and sum the gradient a SECOND time for the step instead of
+// keeping several chunks per lane; the weights are read and written once either way.
+namespace tfrs {
+
+template <int VEC, bool REREAD, bool NT, typename LR>
+__global__ void __launch_bounds__(256) rowwise_adagrad_sorted_kernel(
+    const float *__restrict__ grad_out, const uint32_t *__restrict__ sorted_ids, const uint32_t *__restrict__ perm,
+    int64_t n, int d, uint32_t vocab, float *__restrict__ table, float *__restrict__ accum, const LR lr_arg, float eps,
+    int mode, int piece, const float *__restrict__ part, int group_shift) {
+  const float lr = lr_arg.get();
+  const int per_row = d / VEC;
+  const int group = 1 << group_shift;
+  const int sub = (int)threadIdx.x & (group - 1);
+  const int64_t total = n << group_shift;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t >> group_shift;      // (uniform over the group: its lanes leave or stay together)
+    const uint32_t id = sorted_ids[i];
+    const uint32_t id_prev = sorted_ids[i > 0 ? i - 1 : 0];          // (clamped: the loads are unconditional)
+    const uint32_t id_next = sorted_ids[i + 1 < n ? i + 1 : n - 1];
+    const int64_t src0 = perm[i];
+    if (id >= vocab) continue;                       // invalid / padding id: can never write
+    if (i > 0 && id_prev == id) continue;            // not the start of a run
+    // the run's summed gradient of chunk c: the loads and the order of table_update_sorted_kernel
+    auto grad = [&](int c, float (&g)[VEC]) __attribute__((always_inline)) {
+      auto load = [&](const float *p, float (&r)[VEC], bool nt) __attribute__((always_inline)) {
+        if (VEC == 4) {
+          const float4 e = nt ? nt_load4(reinterpret_cast<const float4 *>(p)) : *reinterpret_cast<const float4 *>(p);
+          r[0] = e.x; r[1 % VEC] = e.y; r[2 % VEC] = e.z; r[3 % VEC] = e.w;
+        } else {
+          r[0] = *p;
+        }
+      };
+      float r[VEC];
+      load(grad_out + (src0 * per_row + c) * VEC, r, NT);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) g[v] = 0.f + r[v];     // (the sum of a run starts from +0, -0 gradients included)
+      int64_t p = i + 1;
+      const int64_t first_end = ((i + piece - 1) / piece + 1) * (int64_t)piece;
+      if (p < n && id_next == id) {
+        for (; p < n && p < first_end && sorted_ids[p] == id; ++p) {
+          load(grad_out + ((int64_t)perm[p] * per_row + c) * VEC, r, false);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) g[v] += r[v];
+        }
+      }
+      if (p == first_end) {
+        for (int64_t b = first_end / piece; b * piece < n && sorted_ids[b * piece] == id; ++b) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) g[v] += part[((b - 1) * per_row + c) * VEC + v];
+        }
+      }
+    };
+    rowwise_adagrad_row<VEC, REREAD, NT>(sub, group, per_row, d, table + (int64_t)id * d, accum + id, lr, eps, mode,
+                                         grad);
+  }
+}
+
+// The row scan with the row-wise epilogue (scatter_rowscan_body_ns<..., ROWWISE = 1>): a wave already owns a row.
+template <typename IdT, typename LR>
+__global__ void __launch_bounds__(256) rowwise_adagrad_rowscan_kernel(
+    const float *__restrict__ grad_out, const void *__restrict__ ids, int64_t n, int d, int64_t vocab,
+    float *__restrict__ table, float *__restrict__ accum, const LR lr_arg, float eps, int mode) {
+  __shared__ int32_t s_ids[kRowscanChunk];
+  __shared__ int s_hits[4 * kRowscanHitCap];
+  const float lr = lr_arg.get();
+  if (d <= 64) scatter_rowscan_body_ns<IdT, 1, 0, void, 1>(grad_out, ids, n, d, vocab, table, accum, lr, eps, mode, blockIdx.x, s_ids, s_hits);
+  else if (d <= 128) scatter_rowscan_body_ns<IdT, 2, 0, void, 1>(grad_out, ids, n, d, vocab, table, accum, lr, eps, mode, blockIdx.x, s_ids, s_hits);
+  else scatter_rowscan_body_ns<IdT, 4, 0, void, 1>(grad_out, ids, n, d, vocab, table, accum, lr, eps, mode, blockIdx.x, s_ids, s_hits);
+}
+
+template <typename LR>
+static int rowwise_adagrad_sparse_launch(const SparseUpdateArgs &a, const LR &lr, float eps, int mode) {
+  hipStream_t s = a.stream;
+  const dim3 block(256);
+  if (a.rowscan) {
+    const dim3 grid((unsigned)((a.vocab + 3) / 4));
+    if (a.ids_are_i64)
+      hipLaunchKernelGGL((rowwise_adagrad_rowscan_kernel<int64_t, LR>), grid, block, 0, s, a.grad_out, a.ids, a.n, a.d, a.vocab, a.table, a.slot0, lr, eps, mode);
+    else
+      hipLaunchKernelGGL((rowwise_adagrad_rowscan_kernel<int32_t, LR>), grid, block, 0, s, a.grad_out, a.ids, a.n, a.d, a.vocab, a.table, a.slot0, lr, eps, mode);
+    TFRS_LAUNCH_CHECK();
+    return TFRS_OK;
+  }
+  uint32_t *keys[2], *vals[2];
+  const int cur = sort_id_positions(a.ids, a.ids_are_i64, a.n, a.vocab, a.workspace, s, keys, vals);
+  TFRS_LAUNCH_CHECK();
+  const bool vec = (a.d % 4 == 0) && (((uintptr_t)a.grad_out | (uintptr_t)a.table) % 16 == 0);
+  const int per_row = vec ? a.d / 4 : a.d;
+  const int shift = rowwise_group_shift(per_row);
+  const bool reread = per_row > 64;
+  const dim3 grid(grid_for(a.n << shift, 256 * 64));
+  // (pieces as in tfrs_embedding_scatter_add_unsorted: their partial sums fit the sort's free ping-pong key buffer)
+  int piece = 32;
+  while (piece < a.d) piece *= 2;
+  float *part = reinterpret_cast<float *>(keys[cur ^ 1]);
+  const int64_t ptotal = ((a.n + piece - 1) / piece) * per_row;
+  const dim3 pgrid(grid_for(ptotal, 256 * 64));
+  const uint32_t vocab = (uint32_t)a.vocab;
+#define TFRS_ROWWISE_SORTED(VEC, REREAD, NT) \
+  hipLaunchKernelGGL((rowwise_adagrad_sorted_kernel<VEC, REREAD, NT, LR>), grid, block, 0, s, a.grad_out, keys[cur], \
+                     vals[cur], a.n, a.d, vocab, a.table, a.slot0, lr, eps, mode, piece, part, shift)
+  if (vec) {
+    hipLaunchKernelGGL((scatter_add_pieces_kernel<4>), pgrid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, piece, part);
+    // the non-temporal row streams above the table size measured for Adagrad (TFRS_SCATTER_NT=0 switches them off)
+    const char *nte = option("TFRS_SCATTER_NT");
+    const bool nt = a.vocab * (int64_t)a.d * 4 > (1ll << 30) && !(nte && nte[0] == '0');
+    if (reread) {
+      if (nt) TFRS_ROWWISE_SORTED(4, true, true);
+      else TFRS_ROWWISE_SORTED(4, true, false);
+    } else {
+      if (nt) TFRS_ROWWISE_SORTED(4, false, true);
+      else TFRS_ROWWISE_SORTED(4, false, false);
+    }
+  } else {
+    hipLaunchKernelGGL((scatter_add_pieces_kernel<1>), pgrid, block, 0, s, a.grad_out, keys[cur], vals[cur], a.n, a.d, vocab, piece, part);
+    if (reread) TFRS_ROWWISE_SORTED(1, true, false);
+    else TFRS_ROWWISE_SORTED(1, false, false);
+  }
+#undef TFRS_ROWWISE_SORTED
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+}  // namespace tfrs
+
+// (lr_dev: NULL, or the device float of tfrs_lr_tick, read once at kernel entry in place of lr)
+extern "C" int tfrs_rowwise_adagrad_sparse(const float *grad_out, const void *ids, int ids_are_i64, int64_t n, int d,
+                                           int64_t vocab, float *table, float *accum, float lr, const float *lr_dev,
+                                           float eps, int mode, int rowscan, void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+  using namespace tfrs;
+  TFRS_CHECK_ARG(mode == 1 || mode == 2, "rowwise_adagrad_sparse: mode must be 1 (sqrt(acc + eps)) or 2 (sqrt(acc) + eps)");
+  TFRS_CHECK_ARG(n >= 0 && d >= 1 && vocab >= 1, "rowwise_adagrad_sparse: bad shape");
+  TFRS_CHECK_ARG(vocab < 0xFFFFFFFFll && n < 0xFFFFFFFFll, "rowwise_adagrad_sparse: vocab / n must fit 32 bits");
+  TFRS_CHECK_ARG(table && accum, "rowwise_adagrad_sparse: NULL pointer");
+  TFRS_CHECK_ARG(eps >= 0.f, "rowwise_adagrad_sparse: epsilon must be non-negative");
+  TFRS_CHECK_ARG(!rowscan || d <= 256, "rowwise_adagrad_sparse: d=%d > 256 on the row-scan route (use the sorted route)", d);
+  if (n == 0) return TFRS_OK;     // nothing is written
+  TFRS_CHECK_ARG(grad_out && ids, "rowwise_adagrad_sparse: NULL pointer");
+  if (!rowscan) {
+    TFRS_CHECK_ARG(workspace, "rowwise_adagrad_sparse: NULL workspace");
+    if (workspace_bytes < tfrs_table_update_workspace_bytes(n, 0)) {
+      set_error("rowwise_adagrad_sparse: workspace too small");
+      return TFRS_ENOMEM;
+    }
+  }
+  const SparseUpdateArgs a = {grad_out, ids, ids_are_i64, n, d, vocab, table, accum, nullptr, rowscan, workspace,
+                              (hipStream_t)stream};
+  if (lr_dev) return rowwise_adagrad_sparse_launch(a, LrDevice{lr_dev}, eps, mode);
+  return rowwise_adagrad_sparse_launch(a, LrValue{lr}, eps, mode);
 }

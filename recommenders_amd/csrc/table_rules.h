@@ -90,6 +90,128 @@ struct FtrlRule {
   }
 };
 
+// ---- optimizers.RowWiseAdagrad: ONE accumulator scalar per table row ("exact row-wise Adagrad") ---------------------
+// G = the row's summed gradient (duplicates summed first, the bits of the other optimizers' sums), d = the row width:
+//   s = (sum_j G_j * G_j) / d;  acc' = acc + s;  den = sqrt(acc' + eps)   (mode 2, legacy: sqrt(acc') + eps)
+//   scale = lr / den  (ONE division per row);  w_j' = w_j - scale * G_j
+// A rule of the kind above cannot express it (apply sees one element), so it has kernels of its own
+// (rowwise_adagrad_sorted_kernel and the ROWWISE epilogue of the row scan in embedding.hip, rowwise_adagrad_dense_kernel
+// in table_update.hip); the arithmetic is the four functions below, contraction off as in every rule.
+//
+// The order of the d additions of sum_j is fixed, so a step is bit-reproducible:
+//   sorted route / dense kernel (rowwise_adagrad_row): a row belongs to a group of L lanes, L the power of two
+//     >= ceil(d / VEC) and at most 64 (VEC = 4 on the float4 path, else 1).  Lane l of the group owns the VEC-wide chunks
+//     l, l + L, l + 2 L, ... of the row and adds their squares to a lane-local partial that starts at +0, chunks in
+//     ascending order, the VEC elements of a chunk in ascending order (a lane without a chunk keeps +0); the L partials
+//     are then summed by an xor butterfly with the offsets L / 2, L / 4, ..., 1 (x += x of lane ^ offset: every lane ends
+//     with the same bits).
+//   row scan (a wave per row): lane l owns the features l, l + 64, l + 128, l + 192, ascending, then the same butterfly
+//     over 64 lanes.
+// The two orders differ (by float32 reassociation of non-negative terms only); which route a table takes is a function
+// of (vocab, n, d) alone.
+__device__ __forceinline__ float rowwise_sq_add(float partial, float g) {
+#pragma clang fp contract(off)
+  return partial + g * g;
+}
+__device__ __forceinline__ float rowwise_group_sum(float x, int group) {
+  for (int o = group >> 1; o > 0; o >>= 1) x += __shfl_xor(x, o);     // (lane ^ o stays inside the aligned group)
+  return x;
+}
+// acc' from the row's sum of squares
+__device__ __forceinline__ float rowwise_accumulate(float acc, float sum_sq, int d) {
+#pragma clang fp contract(off)
+  return acc + sum_sq / (float)d;
+}
+__device__ __forceinline__ float rowwise_scale(float acc_new, float lr, float eps, int mode) {
+#pragma clang fp contract(off)
+  const float den = mode == 2 ? sqrtf(acc_new) + eps : sqrtf(acc_new + eps);
+  return lr / den;
+}
+__device__ __forceinline__ float rowwise_step(float w, float scale, float g) {
+#pragma clang fp contract(off)
+  return w - scale * g;
+}
+
+// One row on its lane group (every lane of the group calls this together; `sub` = the lane's index in the group):
+// grad(c, g) yields the VEC summed gradients of chunk c.  REREAD = false: ceil(d / VEC) <= group, a lane keeps its one
+// chunk of G in registers -- the gradient and the weights are read once.  REREAD = true (wider rows: d > 256 on the
+// float4 path, d > 64 on the scalar path): a lane walks its chunks twice, once for the squares and once for the step, so
+// the gradient is read (and summed) a second time, bit for bit as the first time; the weights are still read once.
+// One lane reads and writes *acc and divides; NT: the row's weights carry the non-temporal hint.
+template <int VEC, bool REREAD, bool NT, typename GradFn>
+__device__ __forceinline__ void rowwise_adagrad_row(int sub, int group, int per_row, int d, float *__restrict__ wrow,
+                                                    float *__restrict__ acc, float lr, float eps, int mode,
+                                                    GradFn grad) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  auto load_w = [&](int c, float (&r)[VEC]) __attribute__((always_inline)) {
+    if (VEC == 4) {
+      const f4 *p = reinterpret_cast<const f4 *>(wrow) + c;
+      const f4 e = NT ? __builtin_nontemporal_load(p) : *p;
+      r[0] = e[0]; r[1 % VEC] = e[1]; r[2 % VEC] = e[2]; r[3 % VEC] = e[3];
+    } else {
+      r[0] = wrow[c];
+    }
+  };
+  auto store_w = [&](int c, const float (&r)[VEC]) __attribute__((always_inline)) {
+    if (VEC == 4) {
+      const f4 e = {r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]};
+      f4 *p = reinterpret_cast<f4 *>(wrow) + c;
+      if (NT) __builtin_nontemporal_store(e, p);
+      else *p = e;
+    } else {
+      wrow[c] = r[0];
+    }
+  };
+  const bool on = sub < per_row;
+  const float a_old = sub == 0 ? *acc : 0.f;
+  float g[VEC], w[VEC];
+  float partial = 0.f;
+  if (!REREAD) {
+    if (on) {
+      load_w(sub, w);
+      grad(sub, g);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) partial = rowwise_sq_add(partial, g[v]);
+    }
+  } else {
+    for (int c = sub; c < per_row; c += group) {
+      grad(c, g);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) partial = rowwise_sq_add(partial, g[v]);
+    }
+  }
+  const float sum_sq = rowwise_group_sum(partial, group);
+  float scale = 0.f;
+  if (sub == 0) {
+    const float a_new = rowwise_accumulate(a_old, sum_sq, d);
+    *acc = a_new;
+    scale = rowwise_scale(a_new, lr, eps, mode);
+  }
+  scale = __shfl(scale, (int)(threadIdx.x & 63u) - sub);
+  if (!REREAD) {
+    if (on) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) w[v] = rowwise_step(w[v], scale, g[v]);
+      store_w(sub, w);
+    }
+  } else {
+    for (int c = sub; c < per_row; c += group) {
+      load_w(c, w);
+      grad(c, g);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) w[v] = rowwise_step(w[v], scale, g[v]);
+      store_w(c, w);
+    }
+  }
+}
+
+// (host) the lane group of a row of `per_row` chunks: the power of two >= per_row, at most 64; returns its log2
+inline int rowwise_group_shift(int64_t per_row) {
+  int shift = 0;
+  while (shift < 6 && (1ll << shift) < per_row) ++shift;
+  return shift;
+}
+
 // The argument checks the C entries share (before any device call).  hyper_h, a HOST array of 8 floats:
 //   SGD   {lr}
 //   Adam  {1 - beta_1, 1 - beta_2, epsilon}, alpha = the device float of tfrs_adam_tick

@@ -1,6 +1,6 @@
 // optimizers.SGD / Adam / Ftrl on dense parameters (one launch for up to 32 tensors, the layout of
 // adagrad_dense_multi_kernel with the rule of table_rules.h as a template parameter), Adam's device-side step
-// counter, and the learning-rate schedules every optimizer evaluates on the device (lr_tick_kernel).  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
+// counter, optimizers.RowWiseAdagrad on a dense 2-D parameter, and the learning-rate schedules every optimizer evaluates on the device (lr_tick_kernel).  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
 #include "common.h"
 #include "table_rules.h"
 
@@ -68,6 +68,59 @@ __global__ void __launch_bounds__(256) table_update_dense_multi_kernel(const Den
 template <typename RULE>
 static int table_update_dense_launch(const DenseUpdateTensors &t, int64_t blocks, const RULE &rule, hipStream_t s) {
   hipLaunchKernelGGL((table_update_dense_multi_kernel<RULE>), dim3((unsigned)blocks), dim3(256), 0, s, t, rule);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+// ---- optimizers.RowWiseAdagrad on a dense 2-D parameter (table_rules.h: one accumulator scalar per row) ------------
+// One lane group per row over ALL rows (the group, REREAD and the arithmetic are those of rowwise_adagrad_sorted_kernel
+// in embedding.hip; the gradient of a chunk is one load).  A row whose gradient is all zero adds 0 to its accumulator and
+// scale * 0 to its weights: it keeps its bits.
+template <int VEC, bool REREAD, typename LR>
+__global__ void __launch_bounds__(256) rowwise_adagrad_dense_kernel(float *__restrict__ param, float *__restrict__ accum,
+                                                                    const float *__restrict__ grad, int64_t rows, int d,
+                                                                    const LR lr_arg, float eps, int mode,
+                                                                    int group_shift) {
+  const float lr = lr_arg.get();
+  const int per_row = d / VEC;
+  const int group = 1 << group_shift;
+  const int sub = (int)threadIdx.x & (group - 1);
+  const int64_t total = rows << group_shift;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = t >> group_shift;      // (uniform over the group)
+    const float *__restrict__ grow = grad + r * d;
+    auto g_of = [&](int c, float (&g)[VEC]) __attribute__((always_inline)) {
+      if (VEC == 4) {
+        const float4 e = reinterpret_cast<const float4 *>(grow)[c];
+        g[0] = e.x; g[1 % VEC] = e.y; g[2 % VEC] = e.z; g[3 % VEC] = e.w;
+      } else {
+        g[0] = grow[c];
+      }
+    };
+    rowwise_adagrad_row<VEC, REREAD, false>(sub, group, per_row, d, param + r * d, accum + r, lr, eps, mode, g_of);
+  }
+}
+
+template <typename LR>
+static int rowwise_adagrad_dense_launch(float *param, float *accum, const float *grad, int64_t rows, int d, const LR &lr,
+                                        float eps, int mode, hipStream_t s) {
+  const bool vec = (d % 4 == 0) && (((uintptr_t)param | (uintptr_t)grad) % 16 == 0);
+  const int per_row = vec ? d / 4 : d;
+  const int shift = rowwise_group_shift(per_row);
+  int64_t blocks = ((rows << shift) + 255) / 256;
+  if (blocks > 256 * 64) blocks = 256 * 64;     // (grid-stride beyond)
+  const dim3 grid((unsigned)blocks), block(256);
+#define TFRS_ROWWISE_DENSE(VEC, REREAD) \
+  hipLaunchKernelGGL((rowwise_adagrad_dense_kernel<VEC, REREAD, LR>), grid, block, 0, s, param, accum, grad, rows, d, lr, \
+                     eps, mode, shift)
+  if (vec) {
+    if (per_row > 64) TFRS_ROWWISE_DENSE(4, true);
+    else TFRS_ROWWISE_DENSE(4, false);
+  } else {
+    if (per_row > 64) TFRS_ROWWISE_DENSE(1, true);
+    else TFRS_ROWWISE_DENSE(1, false);
+  }
+#undef TFRS_ROWWISE_DENSE
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
@@ -224,6 +277,19 @@ extern "C" int tfrs_table_update_dense_multi(int rule, const float *hyper_h, con
   if (rule == kRuleAdam) return table_update_dense_launch(t, blocks, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha}, s);
   if (hyper_h[4] != 0.0f) return table_update_dense_launch(t, blocks, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
   return table_update_dense_launch(t, blocks, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
+}
+
+// (lr_dev: NULL, or the device float of tfrs_lr_tick, read once at kernel entry in place of lr)
+extern "C" int tfrs_rowwise_adagrad_dense(float *param, float *accum, const float *grad, int64_t rows, int d, float lr,
+                                          const float *lr_dev, float eps, int mode, void *stream) {
+  TFRS_CHECK_ARG(mode == 1 || mode == 2, "rowwise_adagrad_dense: mode must be 1 (sqrt(acc + eps)) or 2 (sqrt(acc) + eps)");
+  TFRS_CHECK_ARG(rows >= 0 && d >= 1, "rowwise_adagrad_dense: bad shape");
+  TFRS_CHECK_ARG(rows < (1ll << 40), "rowwise_adagrad_dense: too many rows");
+  TFRS_CHECK_ARG(eps >= 0.f, "rowwise_adagrad_dense: epsilon must be non-negative");
+  if (rows == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(param && accum && grad, "rowwise_adagrad_dense: NULL pointer");
+  if (lr_dev) return rowwise_adagrad_dense_launch(param, accum, grad, rows, d, LrDevice{lr_dev}, eps, mode, (hipStream_t)stream);
+  return rowwise_adagrad_dense_launch(param, accum, grad, rows, d, LrValue{lr}, eps, mode, (hipStream_t)stream);
 }
 
 extern "C" int tfrs_adam_tick(int64_t *step, float *alpha, double learning_rate, double beta_1, double beta_2,

@@ -432,7 +432,7 @@ class Model(torch.nn.Module):
     """``graph=None`` (default): replay captured steps when that is known to be safe -- a ROCm device,
     no gradient exchange (a collective inside a capture is not supported here), and for training an
     optimizer whose step has no host-side state that changes from step to step: this package's
-    ``Adagrad``, ``Adam`` (its counter lives on the device), ``Ftrl``, ``SGD`` and ``experimental.optimizers.ClippyAdagrad`` -- with a
+    ``Adagrad``, ``RowWiseAdagrad``, ``Adam`` (its counter lives on the device), ``Ftrl``, ``SGD`` and ``experimental.optimizers.ClippyAdagrad`` -- with a
     float learning rate or a ``recommenders_amd.schedules`` schedule, which is evaluated on the device --, a ``torch.optim`` optimizer built with
     ``capturable=True`` (a host-side step counter or learning-rate schedule would be frozen into the graph at
     capture time), or a ``CompositeOptimizer`` of such members.
@@ -453,7 +453,7 @@ class Model(torch.nn.Module):
     from recommenders_amd.experimental.optimizers import ClippyAdagrad, CompositeOptimizer
 
     def capturable(opt) -> bool:
-      if isinstance(opt, (own.Adagrad, own.Adam, own.Ftrl, own.SGD, ClippyAdagrad)):
+      if isinstance(opt, (own.Adagrad, own.RowWiseAdagrad, own.Adam, own.Ftrl, own.SGD, ClippyAdagrad)):
         return True
       return bool(opt.param_groups) and all(g.get("capturable", False) for g in opt.param_groups)
 

@@ -56,6 +56,23 @@ TensorFlow's ``ResourceSparseApplyFtrlV2`` is (untouched rows are not written; d
 numerics are reference-unpinned like Adagrad's: the reference's tests hold no vector for them, and the formulas are
 Keras's and TensorFlow's own; ``tools/tf_reference_vectors.py`` writes vectors for a maintainer with TensorFlow.
 
+``RowWiseAdagrad`` is Adagrad with ONE accumulator scalar per table row -- FBGEMM's and torchrec's "exact row-wise
+Adagrad", what DLRM-style models on one GPU are usually trained with: the state of a ``[vocab, d]`` table is ``vocab``
+floats instead of ``vocab * d`` (26 M x 128: 104 MB against 13.3 GB), and the sparse update moves the weights and the
+gradient only.  It is not in the reference; its numerics are reference-unpinned and the formula is the contract.  With
+``G`` the row's summed gradient (duplicates summed first, the bits of the other optimizers' sums) and ``d`` its width,
+all in float32 in the written order without contraction:
+
+    ``s = (sum_j G_j * G_j) / d ;  acc' = acc + s``                      (acc: float32 ``[vocab]``, starts at
+    ``den = sqrt(acc' + epsilon)``   (``legacy``: ``sqrt(acc') + epsilon``)    ``initial_accumulator_value``)
+    ``scale = lr / den ;  w_j' = w_j - scale * G_j``                     (one division per row)
+
+The order of the ``d`` additions is fixed per route (``csrc/table_rules.h``).  Every parameter must be 2-D (a model's
+other tensors go to another optimizer through ``experimental.optimizers.CompositeOptimizer``); the slices of a table go
+through ``tfrs_rowwise_adagrad_sparse`` (the same sort and piece-wise sums as the other rules, then one lane group per
+run; the row scan for small tables), a dense ``.grad`` through ``tfrs_rowwise_adagrad_dense``; ids outside
+``[0, vocab)`` are ignored, untouched rows are not written, a row whose summed gradient is exactly zero keeps its bits.
+
 Schedules.  ``learning_rate`` of every optimizer here (and of ``experimental.optimizers.ClippyAdagrad``) is one of: a
 float; a ``schedules.LearningRateSchedule`` (``recommenders_amd/schedules.py``, also ``optimizers.schedules``); a 0-d
 float32 device tensor; a zero-argument callable returning such a tensor, called once -- the two dynamic forms of the
@@ -401,6 +418,141 @@ class Adagrad(SliceOwningOptimizer):
       # kernels per tensor above were 72 launches of a DCN-v2 step
       for lo in range(0, len(dense), 32):
         _adagrad_dense_multi(dense[lo:lo + 32], lr, eps, 2 if legacy else 1, lr_dev)
+    return loss
+
+
+class RowWiseAdagrad(SliceOwningOptimizer):
+  """Adagrad with ONE accumulator scalar per table row ("exact row-wise Adagrad"; module docstring).  Every parameter is
+  2-D; ``state[p]["accumulator"]`` is float32 ``[p.shape[0]]``."""
+
+  def __init__(self, params: Iterable, learning_rate=0.001, initial_accumulator_value: float = 0.1,
+               epsilon: float = 1e-7, legacy: bool = False):
+    if epsilon < 0.0:
+      raise ValueError("RowWiseAdagrad: epsilon must be non-negative")
+    super().__init__(params, dict(learning_rate=learning_rate,
+                                  initial_accumulator_value=float(initial_accumulator_value),
+                                  epsilon=float(epsilon), legacy=bool(legacy)))
+    for group in self.param_groups:
+      for p in group["params"]:
+        if p.dim() != 2:
+          self.close()
+          raise ValueError(f"RowWiseAdagrad keeps one accumulator per ROW of a 2-D parameter; got a parameter of shape "
+                           f"{tuple(p.shape)}.  Give biases and other tensors to another optimizer (e.g. Adagrad) and "
+                           "pair the two through experimental.optimizers.CompositeOptimizer")
+    self._init_learning_rate()
+
+  def get_config(self) -> Dict[str, Any]:
+    group = self.param_groups[0] if self.param_groups else self.defaults
+    return dict(learning_rate=self._config_learning_rate(group["learning_rate"]),
+                initial_accumulator_value=group["initial_accumulator_value"], epsilon=group["epsilon"],
+                legacy=group["legacy"])
+
+  @classmethod
+  def from_config(cls, params: Iterable, config: Dict[str, Any]) -> "RowWiseAdagrad":
+    return cls(params, **config)
+
+  def _accumulator(self, p: torch.Tensor, init: float) -> torch.Tensor:
+    state = self.state[p]
+    if "accumulator" not in state:
+      state["accumulator"] = torch.full((p.shape[0],), init, dtype=torch.float32, device=p.device)
+    return state["accumulator"]
+
+  def load_state_dict(self, state_dict) -> None:
+    super().load_state_dict(state_dict)
+    # (torch casts loaded state to the parameter's dtype: the accumulator stays float32 whatever the table is)
+    for p, state in self.state.items():
+      if "accumulator" in state:
+        state["accumulator"] = state["accumulator"].to(device=p.device, dtype=torch.float32)
+
+  @staticmethod
+  def _on_kernel_route(p, acc, g) -> bool:
+    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
+            and p.is_contiguous() and acc.is_contiguous() and g.device == p.device)
+
+  @staticmethod
+  def _formula(w, acc, g, lr: float, eps: float, legacy: bool):
+    """The module docstring's rule on same-rowed ``w [r, d]``, ``acc [r]``, ``g [r, d]`` in torch ops, float32 in the
+    kernels' operation order (the order of the ``d`` additions inside the sum is torch's): ``(new w, new acc)``."""
+    g = g.to(torch.float32)
+    s = (g * g).sum(dim=1) / torch.full_like(acc, float(g.shape[1]))     # (a tensor: a true division, not * (1 / d))
+    acc = acc + s
+    den = torch.sqrt(acc) + eps if legacy else torch.sqrt(acc + eps)
+    scale = torch.full_like(acc, lr) / den
+    return (w.to(torch.float32) - scale[:, None] * g).to(w.dtype), acc
+
+  def _sparse_call(self, p, acc, ids, rows, lr, lr_dev, eps, legacy) -> None:
+    from recommenders_amd import _lib
+    lib = _lib.load()
+    d = p.shape[1]
+    if ids.dtype not in (torch.int32, torch.int64):
+      ids = ids.long()
+    flat = ids.reshape(-1).contiguous()
+    n = flat.numel()
+    g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
+    rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
+    # (the row scan needs no workspace: a small table's step is host-bound, an allocation less is measurable)
+    ws = None if rowscan else torch.empty((lib.tfrs_table_update_workspace_bytes(n, 0),), dtype=torch.uint8,
+                                          device=p.device)
+    _lib.check(lib.tfrs_rowwise_adagrad_sparse(
+        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, p.shape[0], _lib.ptr(p.data),
+        _lib.ptr(acc), float(lr), _lib.ptr(lr_dev), float(eps), 2 if legacy else 1, rowscan, _lib.ptr(ws),
+        0 if ws is None else ws.numel(), _lib.current_stream()))
+    self._wrote(p, acc)
+
+  def _sparse_fallback(self, p, acc, ids, rows, lr, eps, legacy) -> None:
+    d = p.shape[1]
+    flat = ids.reshape(-1).long()
+    g = rows.reshape(flat.numel(), d)
+    keep = (flat >= 0) & (flat < p.shape[0])
+    flat, g = flat[keep], g[keep]
+    uniq, inverse = torch.unique(flat, return_inverse=True)
+    # duplicates summed first, in float32 (on the CPU index_add_ adds in occurrence order)
+    summed = torch.zeros((uniq.numel(), d), dtype=torch.float32, device=g.device).index_add_(0, inverse,
+                                                                                             g.to(torch.float32))
+    w, a = self._formula(p.data[uniq], acc[uniq], summed, lr, eps, legacy)
+    p.data[uniq] = w
+    acc[uniq] = a
+
+  def _dense_call(self, p, acc, g, lr, lr_dev, eps, legacy) -> None:
+    from recommenders_amd import _lib
+    _lib.check(_lib.load().tfrs_rowwise_adagrad_dense(
+        _lib.ptr(p.data), _lib.ptr(acc), _lib.ptr(g), p.shape[0], p.shape[1], float(lr), _lib.ptr(lr_dev), float(eps),
+        2 if legacy else 1, _lib.current_stream()))
+    self._wrote(p, acc)
+
+  @staticmethod
+  def _wrote(*tensors) -> None:      # (written through raw pointers)
+    for t in tensors:
+      torch.autograd.graph.increment_version(t)
+
+  @torch.no_grad()
+  def step(self, closure=None):
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    self._tick()
+    for group in self.param_groups:
+      (lr, lr_dev), eps, legacy = self._step_lr(group), group["epsilon"], group.get("legacy", False)
+      host_lr = lambda: self._host_group(group)["learning_rate"]     # (reading a device float synchronises)
+      for p in group["params"]:
+        acc = self._accumulator(p, group["initial_accumulator_value"])
+        merged = self._merged_slices(p)
+        if merged is not None:
+          ids, rows = merged
+          if self._on_kernel_route(p, acc, rows) and ids.device == p.device:
+            self._sparse_call(p, acc, ids, rows, lr, lr_dev, eps, legacy)
+          else:
+            self._sparse_fallback(p, acc, ids.to(p.device), rows.to(p.device), host_lr(), eps, legacy)
+        if p.grad is None:
+          continue
+        g = p.grad
+        if self._on_kernel_route(p, acc, g):
+          self._dense_call(p, acc, g.contiguous(), lr, lr_dev, eps, legacy)
+          continue
+        w, a = self._formula(p.data, acc, g.to_dense() if g.is_sparse else g, host_lr(), eps, legacy)
+        p.data.copy_(w)
+        acc.copy_(a)
     return loss
 
 
