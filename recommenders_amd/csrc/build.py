@@ -33,6 +33,7 @@ SOURCES = [
     "metric_fused.hip",
     "dedup.hip",
     "embedding.hip",
+    "sparse_update.hip",
     "clippy.hip",
     "table_update.hip",
     "shard_route.hip",

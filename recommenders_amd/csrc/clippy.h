@@ -1,5 +1,5 @@
 // ClippyAdagrad (experimental/optimizers/clippy_adagrad.py:188-254 with shrink_by_references, :21-70) -- the element
-// arithmetic shared by the dense kernels (clippy.hip) and the sparse-row kernels (embedding.hip, next to the sort).
+// arithmetic shared by the dense kernels (clippy.hip) and the sparse-row kernels (sparse_update.hip, next to the sort).
 //
 // A variable's clipping factor is a min over the whole variable (or over its touched rows) and has to be known before
 // any element is written, so every update is two passes over the same data: a FACTOR pass (reads only; wave / block
@@ -44,7 +44,12 @@ __device__ __forceinline__ ClippyElement clippy_element(float w, float acc, floa
   e.acc = h.mode == 2 ? fmaf(g, g, acc) : acc;
   const float pre = 1.0f / sqrtf(e.acc + h.eps);
   e.delta = h.lr * g * pre;
-  e.maxd = fabsf(w) * h.var_rel + pre * h.acc_rel + h.abs_thr;
+  {
+    // two products and two sums, each rounded on its own: what every Clippy kernel had compiled to while the choice
+    // was the compiler's; pinned, because the factor scales every touched row and a reshaped kernel flipped the choice
+#pragma clang fp contract(off)
+    e.maxd = fabsf(w) * h.var_rel + pre * h.acc_rel + h.abs_thr;
+  }
   return e;
 }
 

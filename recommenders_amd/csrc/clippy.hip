@@ -1,6 +1,6 @@
 // tfrs_clippy_dense_multi: ClippyAdagrad (experimental/optimizers/clippy_adagrad.py:188-254) on up to 32 dense tensors
 // per call -- the Cross / MLP kernels and biases of a ranking model.  See clippy.h for the two-pass scheme; the sparse
-// rows of embedding tables are handled next to the radix sort in embedding.hip (tfrs_clippy_sparse).
+// rows of embedding tables are handled next to the radix sort in sparse_update.hip (tfrs_clippy_sparse).
 //
 // Traffic: the factor pass reads w, acc, g (12 B / element), the apply pass reads them again and writes w, acc
 // (20 B / element): 32 B against the 20 B of tfrs_adagrad_dense_multi.  Tensor t owns blocks

@@ -1,6 +1,6 @@
 // The update rules of optimizers.SGD / Adam / Ftrl as small structs: a slot count (0, 1 or 2 per-element state tensors
 // beside the weight) and an `apply` on ONE element.  The three update kernels -- the sorted segments and the row scan of
-// embedding.hip, the dense multi-tensor kernel of table_update.hip -- are templates over the rule and are each written
+// sparse_update.hip, the dense multi-tensor kernel of table_update.hip -- are templates over the rule and are each written
 // once.  Hyper-parameters travel by value inside the rule; Adam's bias-corrected step size is read from a device float
 // that adam_tick_kernel (table_update.hip) writes at the head of every step, so a captured step replays with a live t.
 //
@@ -13,8 +13,19 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "row_access.h"
 
 namespace tfrs {
+
+// Denominator of the fused Adagrad update (the sparse kernels of sparse_update.hip, adagrad_dense_multi_kernel of
+// table_update.hip; Adagrad is not a rule below: its arithmetic is compiled with contraction on).  adagrad == 1:
+// sqrt(acc + eps), tf.keras.optimizers.Adagrad of TF >= 2.11 / tf-keras (`variable.assign_sub(lr * grad /
+// sqrt(accumulator + epsilon))`); adagrad == 2: sqrt(acc) + eps, the optimizer_v2 / ResourceApplyAdagradV2 form of
+// TF <= 2.10 (the reference's release script pins TF 2.9.0, tools/build_scripts/release.sh:6) -- also
+// torch.optim.Adagrad's, which the tests cross-check it against.
+__device__ __forceinline__ float adagrad_denom(float acc, float eps, int adagrad) {
+  return adagrad == 2 ? sqrtf(acc) + eps : sqrtf(acc + eps);
+}
 
 // (the `rule` argument of the C entries)
 enum { kRuleSgd = 0, kRuleAdam = 1, kRuleFtrl = 2 };
@@ -95,7 +106,7 @@ struct FtrlRule {
 //   s = (sum_j G_j * G_j) / d;  acc' = acc + s;  den = sqrt(acc' + eps)   (mode 2, legacy: sqrt(acc') + eps)
 //   scale = lr / den  (ONE division per row);  w_j' = w_j - scale * G_j
 // A rule of the kind above cannot express it (apply sees one element), so it has kernels of its own
-// (rowwise_adagrad_sorted_kernel and the ROWWISE epilogue of the row scan in embedding.hip, rowwise_adagrad_dense_kernel
+// (rowwise_adagrad_sorted_kernel and rowscan_rowwise, the row scan's epilogue, in sparse_update.hip, rowwise_adagrad_dense_kernel
 // in table_update.hip); the arithmetic is the four functions below, contraction off as in every rule.
 //
 // The order of the d additions of sum_j is fixed, so a step is bit-reproducible:
@@ -142,26 +153,8 @@ template <int VEC, bool REREAD, bool NT, typename GradFn>
 __device__ __forceinline__ void rowwise_adagrad_row(int sub, int group, int per_row, int d, float *__restrict__ wrow,
                                                     float *__restrict__ acc, float lr, float eps, int mode,
                                                     GradFn grad) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  auto load_w = [&](int c, float (&r)[VEC]) __attribute__((always_inline)) {
-    if (VEC == 4) {
-      const f4 *p = reinterpret_cast<const f4 *>(wrow) + c;
-      const f4 e = NT ? __builtin_nontemporal_load(p) : *p;
-      r[0] = e[0]; r[1 % VEC] = e[1]; r[2 % VEC] = e[2]; r[3 % VEC] = e[3];
-    } else {
-      r[0] = wrow[c];
-    }
-  };
-  auto store_w = [&](int c, const float (&r)[VEC]) __attribute__((always_inline)) {
-    if (VEC == 4) {
-      const f4 e = {r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]};
-      f4 *p = reinterpret_cast<f4 *>(wrow) + c;
-      if (NT) __builtin_nontemporal_store(e, p);
-      else *p = e;
-    } else {
-      wrow[c] = r[0];
-    }
-  };
+  auto load_w = [&](int c, float (&r)[VEC]) __attribute__((always_inline)) { vec_load<VEC, NT>(wrow + c * VEC, r); };
+  auto store_w = [&](int c, const float (&r)[VEC]) __attribute__((always_inline)) { vec_store<VEC, NT>(wrow + c * VEC, r); };
   const bool on = sub < per_row;
   const float a_old = sub == 0 ? *acc : 0.f;
   float g[VEC], w[VEC];

@@ -1,6 +1,8 @@
-// optimizers.SGD / Adam / Ftrl on dense parameters (one launch for up to 32 tensors, the layout of
-// adagrad_dense_multi_kernel with the rule of table_rules.h as a template parameter), Adam's device-side step
-// counter, optimizers.RowWiseAdagrad on a dense 2-D parameter, and the learning-rate schedules every optimizer evaluates on the device (lr_tick_kernel).  The sparse-row kernels of the same rules live in embedding.hip, next to the sort and the row scan.
+// The dense halves of the table optimizers: Adagrad (adagrad_dense_multi_kernel) and optimizers.SGD / Adam / Ftrl (the rule
+// of table_rules.h as a template parameter) on up to 32 dense tensors per launch, Adam's device-side step counter,
+// optimizers.RowWiseAdagrad on a dense 2-D parameter, and the learning-rate schedules every optimizer evaluates on the
+// device (lr_tick_kernel).  The sparse-row kernels of the same optimizers live in sparse_update.hip, next to the sort
+// and the row scan.
 #include "common.h"
 #include "table_rules.h"
 
@@ -65,6 +67,84 @@ __global__ void __launch_bounds__(256) table_update_dense_multi_kernel(const Den
   }
 }
 
+// ---- dense Adagrad of several parameters in ONE launch -------------------------------------------------------------
+// The dense parameters of a ranking model (Cross kernels, MLP kernels and biases: 18 tensors at configs[3]) were
+// updated by four torch kernels each -- addcmul, add, sqrt, addcdiv: 72 launches and 0.43 ms of a 54 ms step, most of
+// them a few KB.  The layout above with s0 the accumulator; same arithmetic as the sparse rows (adagrad_denom):
+// acc += g * g; p -= lr * g / denom(acc).
+template <typename LR = LrValue>
+__global__ void __launch_bounds__(256) adagrad_dense_multi_kernel(const DenseUpdateTensors t, const LR lr_arg, float eps,
+                                                                  int mode) {
+  const float lr = lr_arg.get();
+  int k = 0;
+  while (k + 1 < t.ntensors && (int)blockIdx.x >= t.first_block[k + 1]) ++k;
+  float *__restrict__ p = t.p[k];
+  float *__restrict__ acc = t.s0[k];
+  const float *__restrict__ g = t.g[k];
+  const int64_t n = t.n[k];
+  const int64_t base = (int64_t)((int)blockIdx.x - t.first_block[k]) * kDenseUpdatePerBlock;
+  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  if (vec && base + kDenseUpdatePerBlock <= n) {
+    float4 gv[4], av[4], pv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = base + (int64_t)(u * 256 + threadIdx.x) * 4;
+      gv[u] = *reinterpret_cast<const float4 *>(g + i);
+      av[u] = *reinterpret_cast<const float4 *>(acc + i);
+      pv[u] = *reinterpret_cast<const float4 *>(p + i);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = base + (int64_t)(u * 256 + threadIdx.x) * 4;
+      av[u].x += gv[u].x * gv[u].x; av[u].y += gv[u].y * gv[u].y; av[u].z += gv[u].z * gv[u].z; av[u].w += gv[u].w * gv[u].w;
+      pv[u].x -= lr * gv[u].x / adagrad_denom(av[u].x, eps, mode);
+      pv[u].y -= lr * gv[u].y / adagrad_denom(av[u].y, eps, mode);
+      pv[u].z -= lr * gv[u].z / adagrad_denom(av[u].z, eps, mode);
+      pv[u].w -= lr * gv[u].w / adagrad_denom(av[u].w, eps, mode);
+      *reinterpret_cast<float4 *>(acc + i) = av[u];
+      *reinterpret_cast<float4 *>(p + i) = pv[u];
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < n && i < base + kDenseUpdatePerBlock; i += 256) {
+    const float gi = g[i];
+    const float a = acc[i] + gi * gi;
+    acc[i] = a;
+    p[i] = p[i] - lr * gi / adagrad_denom(a, eps, mode);
+  }
+}
+
+// (host) the argument arrays of a dense multi-tensor entry: `nslots` of the slot arrays (0, 1 or 2) are required, the
+// others are not read.  dense_update_arrays checks the arrays themselves (an entry's own checks come between the two),
+// dense_update_pack the tensors, and fills DenseUpdateTensors and the launch's block count.
+static int dense_update_arrays(const char *who, int ntensors, float *const *params_h, float *const *slot0_h,
+                               float *const *slot1_h, const float *const *grads_h, const int64_t *n_h, int nslots) {
+  TFRS_CHECK_ARG(ntensors >= 1 && ntensors <= 32, "%s: 1..32 tensors", who);
+  TFRS_CHECK_ARG(params_h && grads_h && n_h && (nslots < 1 || slot0_h) && (nslots < 2 || slot1_h),
+                 "%s: NULL argument array", who);
+  return TFRS_OK;
+}
+static int dense_update_pack(const char *who, int ntensors, float *const *params_h, float *const *slot0_h,
+                             float *const *slot1_h, const float *const *grads_h, const int64_t *n_h, int nslots,
+                             DenseUpdateTensors *t, int64_t *blocks_out) {
+  t->ntensors = ntensors;
+  int64_t blocks = 0;
+  for (int i = 0; i < ntensors; ++i) {
+    TFRS_CHECK_ARG(n_h[i] >= 0 && (n_h[i] == 0 || (params_h[i] && grads_h[i] && (nslots < 1 || slot0_h[i]) &&
+                                                   (nslots < 2 || slot1_h[i]))),
+                   "%s: bad tensor %d", who, i);
+    t->first_block[i] = (int)blocks;
+    blocks += (n_h[i] + kDenseUpdatePerBlock - 1) / kDenseUpdatePerBlock;
+    TFRS_CHECK_ARG(blocks < (1ll << 31), "%s: too many elements for one launch", who);
+    t->p[i] = params_h[i]; t->g[i] = grads_h[i]; t->n[i] = n_h[i];
+    t->s0[i] = nslots >= 1 ? slot0_h[i] : nullptr;
+    t->s1[i] = nslots >= 2 ? slot1_h[i] : nullptr;
+  }
+  t->first_block[ntensors] = (int)blocks;
+  *blocks_out = blocks;
+  return TFRS_OK;
+}
+
 template <typename RULE>
 static int table_update_dense_launch(const DenseUpdateTensors &t, int64_t blocks, const RULE &rule, hipStream_t s) {
   hipLaunchKernelGGL((table_update_dense_multi_kernel<RULE>), dim3((unsigned)blocks), dim3(256), 0, s, t, rule);
@@ -74,7 +154,7 @@ static int table_update_dense_launch(const DenseUpdateTensors &t, int64_t blocks
 
 // ---- optimizers.RowWiseAdagrad on a dense 2-D parameter (table_rules.h: one accumulator scalar per row) ------------
 // One lane group per row over ALL rows (the group, REREAD and the arithmetic are those of rowwise_adagrad_sorted_kernel
-// in embedding.hip; the gradient of a chunk is one load).  A row whose gradient is all zero adds 0 to its accumulator and
+// in sparse_update.hip; the gradient of a chunk is one load).  A row whose gradient is all zero adds 0 to its accumulator and
 // scale * 0 to its weights: it keeps its bits.
 template <int VEC, bool REREAD, typename LR>
 __global__ void __launch_bounds__(256) rowwise_adagrad_dense_kernel(float *__restrict__ param, float *__restrict__ accum,
@@ -252,24 +332,13 @@ extern "C" int tfrs_table_update_dense_multi(int rule, const float *hyper_h, con
                                              const float *const *grads_h, const int64_t *n_h, void *stream) {
   int rc = table_rule_check("table_update_dense_multi", rule, hyper_h, alpha);
   if (rc != TFRS_OK) return rc;
-  TFRS_CHECK_ARG(ntensors >= 1 && ntensors <= 32, "table_update_dense_multi: 1..32 tensors");
-  TFRS_CHECK_ARG(params_h && grads_h && n_h && (rule == kRuleSgd || (slot0_h && slot1_h)),
-                 "table_update_dense_multi: NULL argument array");
   DenseUpdateTensors t = {};
-  t.ntensors = ntensors;
   int64_t blocks = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    TFRS_CHECK_ARG(n_h[i] >= 0 && (n_h[i] == 0 || (params_h[i] && grads_h[i] &&
-                                                   (rule == kRuleSgd || (slot0_h[i] && slot1_h[i])))),
-                   "table_update_dense_multi: bad tensor %d", i);
-    t.first_block[i] = (int)blocks;
-    blocks += (n_h[i] + kDenseUpdatePerBlock - 1) / kDenseUpdatePerBlock;
-    TFRS_CHECK_ARG(blocks < (1ll << 31), "table_update_dense_multi: too many elements for one launch");
-    t.p[i] = params_h[i]; t.g[i] = grads_h[i]; t.n[i] = n_h[i];
-    t.s0[i] = rule == kRuleSgd ? nullptr : slot0_h[i];
-    t.s1[i] = rule == kRuleSgd ? nullptr : slot1_h[i];
-  }
-  t.first_block[ntensors] = (int)blocks;
+  const int nslots = rule == kRuleSgd ? 0 : 2;
+  rc = dense_update_arrays("table_update_dense_multi", ntensors, params_h, slot0_h, slot1_h, grads_h, n_h, nslots);
+  if (rc == TFRS_OK)
+    rc = dense_update_pack("table_update_dense_multi", ntensors, params_h, slot0_h, slot1_h, grads_h, n_h, nslots, &t, &blocks);
+  if (rc != TFRS_OK) return rc;
   if (blocks == 0) return TFRS_OK;
   hipStream_t s = (hipStream_t)stream;
   // (for SGD and Ftrl a non-NULL alpha is the device floats of tfrs_lr_tick)
@@ -277,6 +346,33 @@ extern "C" int tfrs_table_update_dense_multi(int rule, const float *hyper_h, con
   if (rule == kRuleAdam) return table_update_dense_launch(t, blocks, AdamRule{hyper_h[0], hyper_h[1], hyper_h[2], alpha}, s);
   if (hyper_h[4] != 0.0f) return table_update_dense_launch(t, blocks, FtrlRule<true>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
   return table_update_dense_launch(t, blocks, FtrlRule<false>{hyper_h[0], hyper_h[1], hyper_h[2], hyper_h[3], alpha}, s);
+}
+
+extern "C" int tfrs_adagrad_dense_multi(int ntensors, float *const *params_h, float *const *accum_h,
+                                        const float *const *grads_h, const int64_t *n_h, float lr, float eps,
+                                        int mode, void *stream) {
+  return tfrs_adagrad_dense_multi_dlr(ntensors, params_h, accum_h, grads_h, n_h, lr, nullptr, eps, mode, stream);
+}
+
+extern "C" int tfrs_adagrad_dense_multi_dlr(int ntensors, float *const *params_h, float *const *accum_h,
+                                            const float *const *grads_h, const int64_t *n_h, float lr,
+                                            const float *lr_dev, float eps, int mode, void *stream) {
+  DenseUpdateTensors t = {};
+  int64_t blocks = 0;
+  int rc = dense_update_arrays("adagrad_dense_multi", ntensors, params_h, accum_h, nullptr, grads_h, n_h, 1);
+  if (rc != TFRS_OK) return rc;
+  TFRS_CHECK_ARG(mode == 1 || mode == 2, "adagrad_dense_multi: mode must be 1 (sqrt(acc + eps)) or 2 (sqrt(acc) + eps)");
+  rc = dense_update_pack("adagrad_dense_multi", ntensors, params_h, accum_h, nullptr, grads_h, n_h, 1, &t, &blocks);
+  if (rc != TFRS_OK) return rc;
+  if (blocks == 0) return TFRS_OK;
+  if (lr_dev)
+    hipLaunchKernelGGL(adagrad_dense_multi_kernel<LrDevice>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t,
+                       LrDevice{lr_dev}, eps, mode);
+  else
+    hipLaunchKernelGGL(adagrad_dense_multi_kernel<LrValue>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t,
+                       LrValue{lr}, eps, mode);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
 }
 
 // (lr_dev: NULL, or the device float of tfrs_lr_tick, read once at kernel entry in place of lr)

@@ -30,7 +30,7 @@ min across ranks).
 """
 
 import ctypes
-from typing import Any, Dict, Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Sequence, Tuple
 
 import torch
 
@@ -124,23 +124,9 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
         [self._factors[i] for i in range(len(all_params))] if export_clipping_factors else [])
     self._init_learning_rate()
 
-  def get_config(self) -> Dict[str, Any]:
-    group = self.param_groups[0] if self.param_groups else self.defaults
-    config = {k: group[k] for k in self._CONFIG}
-    config["learning_rate"] = self._config_learning_rate(config["learning_rate"])
-    return config
-
-  @classmethod
-  def from_config(cls, params: Iterable, config: Dict[str, Any]) -> "ClippyAdagrad":
-    return cls(params, **config)
-
   def _hyper(self, group) -> Tuple[float, float, float, float, float, int]:
     return (self._step_lr(group), group["epsilon"], group["variable_relative_threshold"],
             group["accumulator_relative_threshold"], group["absolute_threshold"], _mode(group))
-
-  def _on_kernel_route(self, p, acc, g) -> bool:
-    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-            and p.is_contiguous() and acc.is_contiguous() and g.device == p.device)
 
   def _dense_call(self, items, first_slot: int, group) -> None:
     """``items``: (parameter, accumulator, gradient) of consecutive factor slots starting at ``first_slot``."""
@@ -151,46 +137,27 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
     args = (n, vp(*[p.data_ptr() for p, _, _ in items]), vp(*[a.data_ptr() for _, a, _ in items]),
             vp(*[g.data_ptr() for _, _, g in items]), i64a(*[p.numel() for p, _, _ in items]),
             ctypes.c_void_p(self._factors.data_ptr() + 4 * first_slot), lr)
-    if lr_dev is None:
-      _lib.check(_lib.load().tfrs_clippy_dense_multi(*args, eps, var_rel, acc_rel, abs_thr, mode,
-                                                     _lib.current_stream()))
-    else:
-      _lib.check(_lib.load().tfrs_clippy_dense_multi_dlr(*args, _lib.ptr(lr_dev), eps, var_rel, acc_rel, abs_thr, mode,
-                                                         _lib.current_stream()))
-    for p, _, _ in items:      # (written through raw pointers)
-      torch.autograd.graph.increment_version(p)
+    _lib.check(_lib.load().tfrs_clippy_dense_multi_dlr(*args, _lib.ptr(lr_dev), eps, var_rel, acc_rel, abs_thr, mode,
+                                                       _lib.current_stream()))
+    self._wrote(*[p for p, _, _ in items])
 
   def _sparse_call(self, p, acc, ids, rows, group) -> None:
     from recommenders_amd import _lib
     lib = _lib.load()
     d = p.shape[1]
-    if ids.dtype not in (torch.int32, torch.int64):
-      ids = ids.long()
-    flat = ids.reshape(-1).contiguous()
+    flat, g = emb._flat_slices(ids, rows, d)
     n = flat.numel()
-    g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
     rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
     ws = torch.empty((lib.tfrs_clippy_sparse_workspace_bytes(n, rowscan),), dtype=torch.uint8, device=p.device)
     (lr, lr_dev), eps, var_rel, acc_rel, abs_thr, mode = self._hyper(group)
-    args = (_lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, p.shape[0], _lib.ptr(p.data),
-            _lib.ptr(acc), ctypes.c_void_p(self._factors.data_ptr() + 4 * self._index[p]), lr)
-    tail = (eps, var_rel, acc_rel, abs_thr, mode, rowscan, _lib.ptr(ws), ws.numel(), _lib.current_stream())
-    if lr_dev is None:
-      _lib.check(lib.tfrs_clippy_sparse(*args, *tail))
-    else:
-      _lib.check(lib.tfrs_clippy_sparse_dlr(*args, _lib.ptr(lr_dev), *tail))
-    torch.autograd.graph.increment_version(p)
+    _lib.check(lib.tfrs_clippy_sparse_dlr(
+        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, p.shape[0], _lib.ptr(p.data),
+        _lib.ptr(acc), ctypes.c_void_p(self._factors.data_ptr() + 4 * self._index[p]), lr, _lib.ptr(lr_dev), eps,
+        var_rel, acc_rel, abs_thr, mode, rowscan, _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+    self._wrote(p)
 
   def _sparse_fallback(self, p, acc, ids, rows, group) -> None:
-    d = p.shape[1]
-    flat = ids.reshape(-1).long()
-    g = rows.reshape(flat.numel(), d)
-    keep = (flat >= 0) & (flat < p.shape[0])
-    flat, g = flat[keep], g[keep]
-    uniq, inverse = torch.unique(flat, return_inverse=True)
-    # duplicates summed first, in the gradient's own precision like the kernels (on the CPU index_add_ adds in
-    # occurrence order)
-    summed = torch.zeros((uniq.numel(), d), dtype=g.dtype, device=g.device).index_add_(0, inverse, g)
+    uniq, summed = self._summed_slices(p, ids, rows, rows.dtype)     # (the gradient's own precision, like the kernels)
     w, a, factor = clippy_update(p.data[uniq], acc[uniq], summed.to(p.dtype), group)
     p.data[uniq] = w
     acc[uniq] = a
@@ -198,10 +165,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
 
   @torch.no_grad()
   def step(self, closure=None):
-    loss = None
-    if closure is not None:
-      with torch.enable_grad():
-        loss = closure()
+    loss = self._closure_loss(closure)
     self._tick()
     for group in self.param_groups:
       init = group["initial_accumulator_value"]
@@ -211,7 +175,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
           continue
         ids, rows = merged
         acc = self._accumulator(p, init)
-        if self._on_kernel_route(p, acc, rows) and ids.device == p.device:
+        if self._on_kernel_route(p, [acc], rows) and ids.device == p.device:
           self._sparse_call(p, acc, ids, rows, group)
         else:
           self._sparse_fallback(p, acc, ids.to(p.device), rows.to(p.device), self._host_group(group))
@@ -222,7 +186,7 @@ class ClippyAdagrad(_base.SliceOwningOptimizer):
         if p.grad is None:
           continue
         g, slot = p.grad, self._index[p]
-        if self._on_kernel_route(p, acc, g):
+        if self._on_kernel_route(p, [acc], g):
           if run and (slot != first + len(run) or len(run) == 32):
             self._dense_call(run, first, group)
             run = []

@@ -51,44 +51,51 @@ def _use_rowscan(vocab: int, n: int, d: int) -> bool:
   return d <= 256 and vocab * max(n, 1) <= _ROWSCAN_MAX_WORK
 
 
+def _flat_slices(ids: torch.Tensor, rows: torch.Tensor, d: int):
+  """The ``(ids, rows)`` slices of a lookup as the sparse kernels take them: the ids as one contiguous int32 / int64
+  vector and the rows as a contiguous ``[n, d]`` matrix (``n``, not ``-1``: a lookup of no ids has ``0 x d`` rows)."""
+  if ids.dtype not in (torch.int32, torch.int64):
+    ids = ids.long()
+  flat = ids.reshape(-1).contiguous()
+  return flat, rows.reshape(flat.numel(), d).contiguous()
+
+
 def scatter_add_rows(grad_out: torch.Tensor, ids: torch.Tensor, vocab: int) -> torch.Tensor:
   """Dense ``[vocab, d]`` gradient of ``gather_rows`` (duplicates summed in occurrence
   order; bit-reproducible)."""
   d = grad_out.shape[-1]
-  g = grad_out.reshape(-1, d).contiguous()
-  if ids.dtype not in (torch.int32, torch.int64):
-    ids = ids.long()
-  if _use_rowscan(vocab, ids.numel(), d):
-    flat = ids.reshape(-1).contiguous()
-    table_grad = torch.empty((vocab, d), dtype=torch.float32, device=g.device)
-    _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan(
-        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, flat.numel(), d,
-        vocab, _lib.ptr(table_grad), None, 0.0, 0.0, 0, _lib.current_stream()))
-    return table_grad
-  flat = ids.reshape(-1).contiguous()
-  table_grad = torch.zeros((vocab, d), dtype=torch.float32, device=g.device)
-  _scatter_unsorted(g, flat, vocab, table_grad, None, 0.0, 0.0, 0)
+  flat, g = _flat_slices(ids, grad_out, d)
+  # (the row scan writes the untouched rows' zeros itself; the sorted route writes touched rows only)
+  fill = torch.empty if _use_rowscan(vocab, flat.numel(), d) else torch.zeros
+  table_grad = fill((vocab, d), dtype=torch.float32, device=g.device)
+  _scatter(g, flat, table_grad, None, 0.0, None, 0.0, 0)
   return table_grad
 
 
 def _scatter_unsorted(g, flat, vocab, dst, accum, lr, eps, adagrad, lr_dev=None) -> None:
   """(id, position) radix sort + segmented scatter-add / fused Adagrad in the library
-  (``tfrs_embedding_scatter_add_unsorted``); ids outside ``[0, vocab)`` are ignored.  ``lr_dev``: the device float
-  the Adagrad epilogue reads its learning rate from (``optimizers`` with a schedule), in place of ``lr``."""
+  (``tfrs_embedding_scatter_add_unsorted_dlr``); ids outside ``[0, vocab)`` are ignored.  ``lr_dev``: ``None``, or the
+  device float the Adagrad epilogue reads its learning rate from (``optimizers`` with a schedule) in place of ``lr``."""
   lib = _lib.load()
   n = flat.numel()
   ws = torch.empty((lib.tfrs_embedding_scatter_add_workspace_bytes(n),), dtype=torch.uint8,
                    device=g.device)
-  if lr_dev is not None:
-    _lib.check(lib.tfrs_embedding_scatter_add_unsorted_dlr(
-        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, g.shape[-1], vocab,
-        _lib.ptr(dst), _lib.ptr(accum), float(lr), _lib.ptr(lr_dev), float(eps), adagrad, _lib.ptr(ws), ws.numel(),
-        _lib.current_stream()))
-    return
-  _lib.check(lib.tfrs_embedding_scatter_add_unsorted(
+  _lib.check(lib.tfrs_embedding_scatter_add_unsorted_dlr(
       _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, g.shape[-1], vocab,
-      _lib.ptr(dst), _lib.ptr(accum), float(lr), float(eps), adagrad, _lib.ptr(ws), ws.numel(),
+      _lib.ptr(dst), _lib.ptr(accum), float(lr), _lib.ptr(lr_dev), float(eps), adagrad, _lib.ptr(ws), ws.numel(),
       _lib.current_stream()))
+
+
+def _scatter(g, flat, dst, accum, lr, lr_dev, eps, adagrad) -> None:
+  """Scatter-add (``adagrad`` 0) or the fused Adagrad update (1 / 2: the denominator's mode) of flat slices into
+  ``dst [vocab, d]``: the row scan for small tables (``tfrs_embedding_scatter_add_rowscan_dlr``), else the sort."""
+  n, d, vocab = flat.numel(), g.shape[-1], dst.shape[0]
+  if not _use_rowscan(vocab, n, d):
+    _scatter_unsorted(g, flat, vocab, dst, accum, lr, eps, adagrad, lr_dev)
+    return
+  _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_dlr(
+      _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, n, d, vocab, _lib.ptr(dst), _lib.ptr(accum),
+      float(lr), _lib.ptr(lr_dev), float(eps), adagrad, _lib.current_stream()))
 
 
 def adagrad_sparse_update_(table: torch.Tensor, accum: torch.Tensor, grad_out: torch.Tensor,
@@ -98,40 +105,21 @@ def adagrad_sparse_update_(table: torch.Tensor, accum: torch.Tensor, grad_out: t
   (``models/base.py:77-78`` with ``Adagrad``, ``README.md:84``):
   g = sum of duplicate grads; acc += g*g; row -= lr * g / sqrt(acc + eps)
   (``legacy``: ``/ (sqrt(acc) + eps)``, the optimizer_v2 form of TF <= 2.10 and ``torch.optim.Adagrad``)."""
-  mode = 2 if legacy else 1
-  d = grad_out.shape[-1]
-  g = grad_out.reshape(-1, d).contiguous()
-  if ids.dtype not in (torch.int32, torch.int64):
-    ids = ids.long()
-  if _use_rowscan(table.shape[0], ids.numel(), d):
-    flat = ids.reshape(-1).contiguous()
-    if lr_dev is not None:
-      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_dlr(
-          _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, flat.numel(), d,
-          table.shape[0], _lib.ptr(table), _lib.ptr(accum), float(lr), _lib.ptr(lr_dev), float(eps), mode,
-          _lib.current_stream()))
-      return
-    _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan(
-        _lib.ptr(g), _lib.ptr(flat), 1 if flat.dtype == torch.int64 else 0, flat.numel(), d,
-        table.shape[0], _lib.ptr(table), _lib.ptr(accum), float(lr), float(eps), mode,
-        _lib.current_stream()))
-    return
-  _scatter_unsorted(g, ids.reshape(-1).contiguous(), table.shape[0], table, accum, lr, eps, mode, lr_dev)
+  flat, g = _flat_slices(ids, grad_out, grad_out.shape[-1])
+  _scatter(g, flat, table, accum, lr, lr_dev, eps, 2 if legacy else 1)
 
 
 def adagrad_sparse_update_multi_(updates, lr: float, eps: float = 1e-7, legacy: bool = False,
                                  lr_dev: Optional[torch.Tensor] = None) -> None:
   """``adagrad_sparse_update_`` for several tables of one optimizer step; ``updates`` is a list of
   ``(table, accum, grad_rows, ids)``.  The small tables (row-scan path) of the step go out in
-  ONE launch (``tfrs_embedding_scatter_add_rowscan_multi``): each table's update is a chain of
+  ONE launch (``tfrs_embedding_scatter_add_rowscan_multi_dlr``): each table's update is a chain of
   dependent latencies, so separate launches pay the chain once per table."""
   small, rest = [], []
   for table, accum, grad_out, ids in updates:
     d = grad_out.shape[-1]
-    if ids.dtype not in (torch.int32, torch.int64):
-      ids = ids.long()
-    (small if _use_rowscan(table.shape[0], ids.numel(), d) else rest).append(
-        (table, accum, grad_out.reshape(-1, d).contiguous(), ids.reshape(-1).contiguous()))
+    flat, g = _flat_slices(ids, grad_out, d)
+    (small if _use_rowscan(table.shape[0], flat.numel(), d) else rest).append((table, accum, g, flat))
   for table, accum, g, ids in rest:
     adagrad_sparse_update_(table, accum, g, ids, lr, eps, legacy, lr_dev)
   for lo in range(0, len(small), 8):
@@ -148,12 +136,8 @@ def adagrad_sparse_update_multi_(updates, lr: float, eps: float = 1e-7, legacy: 
             i64a(*[i.numel() for _, _, _, i in grp]), ia(*[g.shape[-1] for _, _, g, _ in grp]),
             i64a(*[t.shape[0] for t, _, _, _ in grp]), vp(*[t.data_ptr() for t, _, _, _ in grp]),
             vp(*[a.data_ptr() for _, a, _, _ in grp]), float(lr))
-    if lr_dev is not None:
-      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi_dlr(
-          *args, _lib.ptr(lr_dev), float(eps), 2 if legacy else 1, _lib.current_stream()))
-    else:
-      _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi(
-          *args, float(eps), 2 if legacy else 1, _lib.current_stream()))
+    _lib.check(_lib.load().tfrs_embedding_scatter_add_rowscan_multi_dlr(
+        *args, _lib.ptr(lr_dev), float(eps), 2 if legacy else 1, _lib.current_stream()))
 
 
 def _emit_table_grad(ctx, grad_out):

@@ -12,7 +12,8 @@ touches the rows that were looked up: duplicate ids are summed first, then the u
 applied once per unique row.  For parameters of :class:`recommenders_amd.layers.embedding.Embedding`
 the gradient never exists as a dense ``[vocab, dim]`` tensor -- the lookup's backward hands
 ``(ids, grad_rows)`` slices to the optimizer, which runs the fused sort + segmented
-scatter-add + Adagrad kernel (``tfrs_embedding_scatter_add_bwd`` with ``adagrad=1``).
+scatter-add + Adagrad kernel (``tfrs_embedding_scatter_add_unsorted_dlr`` with ``adagrad=1``; every sparse update of
+this module is in ``csrc/sparse_update.hip``, the dense halves in ``csrc/table_update.hip``).
 Dense parameters (Cross kernels, MLPs) take the same formula element-wise.
 
 The reference's tests do not pin Adagrad numerics ("parity unpinned"); the
@@ -101,19 +102,14 @@ from recommenders_amd.layers import embedding as emb
 
 
 def _adagrad_dense_multi(items, lr: float, eps: float, mode: int, lr_dev: Optional[torch.Tensor] = None) -> None:
-  import ctypes
   from recommenders_amd import _lib
   n = len(items)
   vp, i64a = ctypes.c_void_p * n, ctypes.c_int64 * n
   args = (n, vp(*[p.data_ptr() for p, _, _ in items]), vp(*[a.data_ptr() for _, a, _ in items]),
           vp(*[g.data_ptr() for _, _, g in items]), i64a(*[p.numel() for p, _, _ in items]), float(lr))
-  if lr_dev is None:
-    _lib.check(_lib.load().tfrs_adagrad_dense_multi(*args, float(eps), int(mode), _lib.current_stream()))
-  else:
-    _lib.check(_lib.load().tfrs_adagrad_dense_multi_dlr(*args, _lib.ptr(lr_dev), float(eps), int(mode),
-                                                        _lib.current_stream()))
-  for p, _, _ in items:      # (written through raw pointers)
-    torch.autograd.graph.increment_version(p)
+  _lib.check(_lib.load().tfrs_adagrad_dense_multi_dlr(*args, _lib.ptr(lr_dev), float(eps), int(mode),
+                                                      _lib.current_stream()))
+  SliceOwningOptimizer._wrote(*[p for p, _, _ in items])
 
 
 def _is_dynamic(lr) -> bool:
@@ -126,10 +122,15 @@ class SliceOwningOptimizer(torch.optim.Optimizer):
   (``Adagrad``, ``experimental.optimizers.ClippyAdagrad``): ownership of the tables' sparse-gradient mode
   (``_tfrs_sparse_grad`` / ``_tfrs_slices`` / ``_tfrs_sparse_owner``), ``close``, the per-parameter accumulator,
   ``reset_state_``, ``zero_grad`` and the version bumps after raw-pointer writes.  Subclasses pass their
-  hyper-parameters as ``defaults`` (``initial_accumulator_value`` among them, for those that keep an accumulator) and
-  implement ``step``."""
+  hyper-parameters as ``defaults`` (``initial_accumulator_value`` among them, for those that keep an accumulator), name
+  the constructor arguments in ``_CONFIG`` and implement ``step``; the route test, the torch route's dedupe of slices and
+  the re-cast of loaded state are here as well."""
 
   _COUNTER = "iterations"     # the state key of the device counter (``Adam``: its ``step``)
+  _CONFIG = ()                # the constructor's keyword arguments, all of them keys of a parameter group
+  # state that keeps its own dtype whatever the parameter's is (``load_state_dict``); subclasses add to it
+  _STATE_DTYPES = {"iterations": torch.int64, "learning_rate": torch.float32, "step": torch.int64,
+                   "alpha": torch.float32}
 
   def __init__(self, params: Iterable, defaults: dict):
     if defaults.get("initial_accumulator_value", 0.0) < 0.0:
@@ -272,19 +273,61 @@ class SliceOwningOptimizer(torch.optim.Optimizer):
       return schedules.serialize(lr)
     return float(lr)
 
+  def get_config(self) -> Dict[str, Any]:
+    group = self.param_groups[0] if self.param_groups else self.defaults
+    config = {k: group[k] for k in self._CONFIG}
+    config["learning_rate"] = self._config_learning_rate(config["learning_rate"])
+    return config
+
+  @classmethod
+  def from_config(cls, params: Iterable, config: Dict[str, Any]):
+    return cls(params, **config)
+
   def load_state_dict(self, state_dict) -> None:
     super().load_state_dict(state_dict)
-    # (torch casts loaded state to the parameter's dtype: the int64 counter is taken from the saved state itself)
+    # (torch casts loaded state to the parameter's dtype: the entries of _STATE_DTYPES are taken from the saved state
+    # itself, in their own dtype, onto the parameter's device)
     saved = state_dict["state"]
     ids = [i for group in state_dict["param_groups"] for i in group["params"]]
     params = [p for group in self.param_groups for p in group["params"]]
     for i, p in zip(ids, params):
-      entry = saved.get(i, {})
-      if "iterations" in entry:
-        self.state[p]["iterations"] = entry["iterations"].detach().clone().to(device=p.device, dtype=torch.int64)
-      if "learning_rate" in entry:
-        self.state[p]["learning_rate"] = entry["learning_rate"].detach().clone().to(device=p.device,
-                                                                                   dtype=torch.float32)
+      for key, value in saved.get(i, {}).items():
+        if key in self._STATE_DTYPES:
+          self.state[p][key] = value.detach().clone().to(device=p.device, dtype=self._STATE_DTYPES[key])
+
+  @staticmethod
+  def _closure_loss(closure):
+    """Head of every ``step(closure)``."""
+    if closure is None:
+      return None
+    with torch.enable_grad():
+      return closure()
+
+  @staticmethod
+  def _on_kernel_route(p, state_tensors, g) -> bool:
+    """Whether parameter ``p`` with its per-parameter state and the gradient (or gradient rows) ``g`` can go to the HIP
+    kernels; anything else takes the torch formulas."""
+    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
+            and p.is_contiguous() and all(s.is_contiguous() for s in state_tensors) and g.device == p.device)
+
+  @staticmethod
+  def _wrote(*tensors) -> None:
+    """Version counters of tensors the kernels wrote through raw pointers, so that anything keyed on them (Streaming's
+    packed-block cache over views of a table) sees the change."""
+    for t in tensors:
+      torch.autograd.graph.increment_version(t)
+
+  @staticmethod
+  def _summed_slices(p, ids, rows, dtype):
+    """The torch route's view of the slices of table ``p``: ``(unique ids, their summed rows [u, d])`` -- ids outside
+    ``[0, vocab)`` dropped, duplicates summed first in ``dtype`` (on the CPU ``index_add_`` adds in occurrence order)."""
+    flat = ids.reshape(-1).long()
+    g = rows.reshape(flat.numel(), p.shape[1])
+    keep = (flat >= 0) & (flat < p.shape[0])
+    flat, g = flat[keep], g[keep]
+    uniq, inverse = torch.unique(flat, return_inverse=True)
+    return uniq, torch.zeros((uniq.numel(), p.shape[1]), dtype=dtype, device=g.device).index_add_(0, inverse,
+                                                                                                  g.to(dtype))
 
   def _owns(self, p) -> bool:
     owner = getattr(p, "_tfrs_sparse_owner", None)
@@ -361,6 +404,8 @@ class SliceOwningOptimizer(torch.optim.Optimizer):
 class Adagrad(SliceOwningOptimizer):
   """``tf.keras.optimizers.Adagrad(learning_rate, initial_accumulator_value, epsilon)``."""
 
+  _CONFIG = ("learning_rate", "initial_accumulator_value", "epsilon", "legacy")
+
   def __init__(self, params: Iterable, learning_rate=0.001,
                initial_accumulator_value: float = 0.1, epsilon: float = 1e-7, legacy: bool = False):
     super().__init__(params, dict(learning_rate=learning_rate,
@@ -368,22 +413,9 @@ class Adagrad(SliceOwningOptimizer):
                                   epsilon=float(epsilon), legacy=bool(legacy)))
     self._init_learning_rate()
 
-  def get_config(self) -> Dict[str, Any]:
-    group = self.param_groups[0] if self.param_groups else self.defaults
-    return dict(learning_rate=self._config_learning_rate(group["learning_rate"]),
-                initial_accumulator_value=group["initial_accumulator_value"], epsilon=group["epsilon"],
-                legacy=group["legacy"])
-
-  @classmethod
-  def from_config(cls, params: Iterable, config: Dict[str, Any]) -> "Adagrad":
-    return cls(params, **config)
-
   @torch.no_grad()
   def step(self, closure=None):
-    loss = None
-    if closure is not None:
-      with torch.enable_grad():
-        loss = closure()
+    loss = self._closure_loss(closure)
     self._tick()
     for group in self.param_groups:
       (lr, lr_dev), eps, legacy = self._step_lr(group), group["epsilon"], group.get("legacy", False)
@@ -398,17 +430,13 @@ class Adagrad(SliceOwningOptimizer):
           touched.append(p)
       if sparse:
         emb.adagrad_sparse_update_multi_(sparse, lr, eps, legacy, lr_dev=lr_dev)   # small tables: one launch for all
-        # the kernels wrote through raw pointers: bump the version counters so that anything
-        # keyed on them (Streaming's packed-block cache over views of a table) sees the change
-        for table in touched:
-          torch.autograd.graph.increment_version(table)
+        self._wrote(*touched)
       dense = []      # (parameter, accumulator, gradient) of every dense parameter of the group on a GPU
       for p in group["params"]:
         acc = self._accumulator(p, group["initial_accumulator_value"])
         if p.grad is not None:
           g = p.grad
-          if (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-              and p.is_contiguous() and acc.is_contiguous()):
+          if self._on_kernel_route(p, [acc], g):
             dense.append((p, acc, g.contiguous()))
             continue
           acc.addcmul_(g, g)
@@ -424,6 +452,9 @@ class Adagrad(SliceOwningOptimizer):
 class RowWiseAdagrad(SliceOwningOptimizer):
   """Adagrad with ONE accumulator scalar per table row ("exact row-wise Adagrad"; module docstring).  Every parameter is
   2-D; ``state[p]["accumulator"]`` is float32 ``[p.shape[0]]``."""
+
+  _CONFIG = Adagrad._CONFIG
+  _STATE_DTYPES = dict(SliceOwningOptimizer._STATE_DTYPES, accumulator=torch.float32)    # (whatever the table is)
 
   def __init__(self, params: Iterable, learning_rate=0.001, initial_accumulator_value: float = 0.1,
                epsilon: float = 1e-7, legacy: bool = False):
@@ -441,33 +472,11 @@ class RowWiseAdagrad(SliceOwningOptimizer):
                            "pair the two through experimental.optimizers.CompositeOptimizer")
     self._init_learning_rate()
 
-  def get_config(self) -> Dict[str, Any]:
-    group = self.param_groups[0] if self.param_groups else self.defaults
-    return dict(learning_rate=self._config_learning_rate(group["learning_rate"]),
-                initial_accumulator_value=group["initial_accumulator_value"], epsilon=group["epsilon"],
-                legacy=group["legacy"])
-
-  @classmethod
-  def from_config(cls, params: Iterable, config: Dict[str, Any]) -> "RowWiseAdagrad":
-    return cls(params, **config)
-
   def _accumulator(self, p: torch.Tensor, init: float) -> torch.Tensor:
     state = self.state[p]
     if "accumulator" not in state:
       state["accumulator"] = torch.full((p.shape[0],), init, dtype=torch.float32, device=p.device)
     return state["accumulator"]
-
-  def load_state_dict(self, state_dict) -> None:
-    super().load_state_dict(state_dict)
-    # (torch casts loaded state to the parameter's dtype: the accumulator stays float32 whatever the table is)
-    for p, state in self.state.items():
-      if "accumulator" in state:
-        state["accumulator"] = state["accumulator"].to(device=p.device, dtype=torch.float32)
-
-  @staticmethod
-  def _on_kernel_route(p, acc, g) -> bool:
-    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-            and p.is_contiguous() and acc.is_contiguous() and g.device == p.device)
 
   @staticmethod
   def _formula(w, acc, g, lr: float, eps: float, legacy: bool):
@@ -484,11 +493,8 @@ class RowWiseAdagrad(SliceOwningOptimizer):
     from recommenders_amd import _lib
     lib = _lib.load()
     d = p.shape[1]
-    if ids.dtype not in (torch.int32, torch.int64):
-      ids = ids.long()
-    flat = ids.reshape(-1).contiguous()
+    flat, g = emb._flat_slices(ids, rows, d)
     n = flat.numel()
-    g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
     rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
     # (the row scan needs no workspace: a small table's step is host-bound, an allocation less is measurable)
     ws = None if rowscan else torch.empty((lib.tfrs_table_update_workspace_bytes(n, 0),), dtype=torch.uint8,
@@ -500,15 +506,7 @@ class RowWiseAdagrad(SliceOwningOptimizer):
     self._wrote(p, acc)
 
   def _sparse_fallback(self, p, acc, ids, rows, lr, eps, legacy) -> None:
-    d = p.shape[1]
-    flat = ids.reshape(-1).long()
-    g = rows.reshape(flat.numel(), d)
-    keep = (flat >= 0) & (flat < p.shape[0])
-    flat, g = flat[keep], g[keep]
-    uniq, inverse = torch.unique(flat, return_inverse=True)
-    # duplicates summed first, in float32 (on the CPU index_add_ adds in occurrence order)
-    summed = torch.zeros((uniq.numel(), d), dtype=torch.float32, device=g.device).index_add_(0, inverse,
-                                                                                             g.to(torch.float32))
+    uniq, summed = self._summed_slices(p, ids, rows, torch.float32)
     w, a = self._formula(p.data[uniq], acc[uniq], summed, lr, eps, legacy)
     p.data[uniq] = w
     acc[uniq] = a
@@ -520,17 +518,9 @@ class RowWiseAdagrad(SliceOwningOptimizer):
         2 if legacy else 1, _lib.current_stream()))
     self._wrote(p, acc)
 
-  @staticmethod
-  def _wrote(*tensors) -> None:      # (written through raw pointers)
-    for t in tensors:
-      torch.autograd.graph.increment_version(t)
-
   @torch.no_grad()
   def step(self, closure=None):
-    loss = None
-    if closure is not None:
-      with torch.enable_grad():
-        loss = closure()
+    loss = self._closure_loss(closure)
     self._tick()
     for group in self.param_groups:
       (lr, lr_dev), eps, legacy = self._step_lr(group), group["epsilon"], group.get("legacy", False)
@@ -540,14 +530,14 @@ class RowWiseAdagrad(SliceOwningOptimizer):
         merged = self._merged_slices(p)
         if merged is not None:
           ids, rows = merged
-          if self._on_kernel_route(p, acc, rows) and ids.device == p.device:
+          if self._on_kernel_route(p, [acc], rows) and ids.device == p.device:
             self._sparse_call(p, acc, ids, rows, lr, lr_dev, eps, legacy)
           else:
             self._sparse_fallback(p, acc, ids.to(p.device), rows.to(p.device), host_lr(), eps, legacy)
         if p.grad is None:
           continue
         g = p.grad
-        if self._on_kernel_route(p, acc, g):
+        if self._on_kernel_route(p, [acc], g):
           self._dense_call(p, acc, g.contiguous(), lr, lr_dev, eps, legacy)
           continue
         w, a = self._formula(p.data, acc, g.to_dense() if g.is_sparse else g, host_lr(), eps, legacy)
@@ -564,17 +554,6 @@ class _RuleOptimizer(SliceOwningOptimizer):
 
   _RULE = -1        # the `rule` argument of the C entries
   _SLOTS = ()       # state keys of the per-element slots, in kernel order
-  _CONFIG = ()
-
-  def get_config(self) -> Dict[str, Any]:
-    group = self.param_groups[0] if self.param_groups else self.defaults
-    config = {k: group[k] for k in self._CONFIG}
-    config["learning_rate"] = self._config_learning_rate(config["learning_rate"])
-    return config
-
-  @classmethod
-  def from_config(cls, params: Iterable, config: Dict[str, Any]):
-    return cls(params, **config)
 
   # -- what a rule defines ---------------------------------------------------------------------------------------------
   def _slot_init(self, group, key: str) -> float:
@@ -617,35 +596,13 @@ class _RuleOptimizer(SliceOwningOptimizer):
           if key in state:
             state[key].zero_()
 
-  def load_state_dict(self, state_dict) -> None:
-    super().load_state_dict(state_dict)
-    # (torch casts loaded state to the parameter's dtype, and leaves "step" wherever it was saved)
-    for p, state in self.state.items():
-      if "step" in state:
-        state["step"] = state["step"].to(device=p.device, dtype=torch.int64)
-      if "alpha" in state:
-        state["alpha"] = state["alpha"].to(device=p.device, dtype=torch.float32)
-
   # -- the update ------------------------------------------------------------------------------------------------------
-  @staticmethod
-  def _on_kernel_route(p, slots, g) -> bool:
-    return (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-            and p.is_contiguous() and all(s.is_contiguous() for s in slots) and g.device == p.device)
-
-  @staticmethod
-  def _wrote(*tensors) -> None:      # (written through raw pointers)
-    for t in tensors:
-      torch.autograd.graph.increment_version(t)
-
   def _sparse_call(self, p, slots, ids, rows, hyper, alpha) -> None:
     from recommenders_amd import _lib
     lib = _lib.load()
     d = p.shape[1]
-    if ids.dtype not in (torch.int32, torch.int64):
-      ids = ids.long()
-    flat = ids.reshape(-1).contiguous()
+    flat, g = emb._flat_slices(ids, rows, d)
     n = flat.numel()
-    g = rows.reshape(n, d).contiguous()     # (n, not -1: a lookup of no ids has 0 x d rows)
     rowscan = 1 if emb._use_rowscan(p.shape[0], n, d) else 0
     ws = torch.empty((lib.tfrs_table_update_workspace_bytes(n, rowscan),), dtype=torch.uint8, device=p.device)
     s0, s1 = (list(slots) + [None, None])[:2]
@@ -656,15 +613,7 @@ class _RuleOptimizer(SliceOwningOptimizer):
     self._wrote(p, *slots)
 
   def _sparse_fallback(self, p, slots, ids, rows, group, alpha) -> None:
-    d = p.shape[1]
-    flat = ids.reshape(-1).long()
-    g = rows.reshape(flat.numel(), d)
-    keep = (flat >= 0) & (flat < p.shape[0])
-    flat, g = flat[keep], g[keep]
-    uniq, inverse = torch.unique(flat, return_inverse=True)
-    # duplicates summed first, in the gradient's own precision like the kernels (on the CPU index_add_ adds in
-    # occurrence order)
-    summed = torch.zeros((uniq.numel(), d), dtype=g.dtype, device=g.device).index_add_(0, inverse, g)
+    uniq, summed = self._summed_slices(p, ids, rows, rows.dtype)     # (the gradient's own precision, like the kernels)
     w, new = self._formula(p.data[uniq], [s[uniq] for s in slots], summed.to(p.dtype), group, alpha)
     p.data[uniq] = w
     for s, value in zip(slots, new):
@@ -683,10 +632,7 @@ class _RuleOptimizer(SliceOwningOptimizer):
 
   @torch.no_grad()
   def step(self, closure=None):
-    loss = None
-    if closure is not None:
-      with torch.enable_grad():
-        loss = closure()
+    loss = self._closure_loss(closure)
     self._begin_step()
     for group in self.param_groups:
       hyper = (ctypes.c_float * 8)(*self._hyper(group))

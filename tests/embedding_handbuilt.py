@@ -1,4 +1,4 @@
-"""Hand-built id lists for the embedding kernels (csrc/embedding.hip): every builder returns the ids together with a
+"""Hand-built id lists for the embedding kernels (csrc/embedding.hip, csrc/sparse_update.hip): every builder returns the ids together with a
 description of the structure it planted, so a test chooses the layout the kernels see -- run starts and lengths against
 the piece cuts of the sorted route, occurrences against the LDS chunks and the hit list of the row scan, bag lengths
 against the rounds of the combiner -- instead of taking what a random draw produces.  tests/test_embedding_handbuilt_host.py

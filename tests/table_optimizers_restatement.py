@@ -5,8 +5,8 @@ same float32 inputs.  Duplicates of a sparse gradient are summed in float32 in o
 (``clippy_restatement.sum_duplicates``: the project's contract for IndexedSlices), so the summed gradient is an input,
 not an error source.  Test infrastructure only.
 
-What the build guarantees (recommenders_amd/csrc/build.py: ``-O3 -std=c++17 -fPIC`` and nothing else for embedding.hip
-and table_update.hip -- no fast-math flag, so hipcc's default ``-fhip-fp32-correctly-rounded-divide-sqrt`` holds):
+What the build guarantees (recommenders_amd/csrc/build.py: ``-O3 -std=c++17 -fPIC`` and nothing else for
+sparse_update.hip and table_update.hip -- no fast-math flag, so hipcc's default ``-fhip-fp32-correctly-rounded-divide-sqrt`` holds):
 division and ``sqrtf`` are correctly rounded.  hipcc contracts ``a * b + c`` by default; csrc/table_rules.h switches
 contraction off inside every rule, so each operation rounds on its own as in NumPy.
 

@@ -906,7 +906,7 @@ def test_embedding_path_at_config_table_sizes(rows, d, n):
   ref = o_emb.scatter_add_grad(g, remap, uniq.size)
   np.testing.assert_array_equal(_np(dense[touched]), ref)
   assert float(dense[torch.as_tensor(untouched).cuda()].abs().max()) == 0.0
-  # very hot rows (runs of 4000 >> piece: summed as partial sums of pieces, csrc/embedding.hip): float64
+  # very hot rows (runs of 4000 >> piece: summed as partial sums of pieces, csrc/sparse_update.h): float64
   # reference, gate relative to the sum of |terms|
   del dense
   vh = np.array([rows - 1, edge, 5], dtype=np.int64)

@@ -1,4 +1,4 @@
-"""The embedding kernels (csrc/embedding.hip) on hand-built id lists (tests/embedding_handbuilt.py, proved on the host by
+"""The embedding kernels (csrc/embedding.hip, csrc/sparse_update.hip) on hand-built id lists (tests/embedding_handbuilt.py, proved on the host by
 tests/test_embedding_handbuilt_host.py) at the edges of their layouts that random ids do not reach.
 
   a. gather_kernel: the tail loop behind the 4-way unrolled one, per_row = 3 and 65, VEC = 1 at d % 4 != 0 and at a
@@ -7,7 +7,7 @@ tests/test_embedding_handbuilt_host.py) at the edges of their layouts that rando
   b. segment_reduce_kernel / segment_reduce_bwd_kernel: bags of 0, 1, 7, 8, 9, 16, 17 and 40 entries (a partly clamped
      round, full rounds, a second round, a last bag whose clamp lands on the final id), int32 and int64 ids / splits,
      VEC = 4 and VEC = 1 (d % 4 != 0, a misaligned gradient), all combiners, exact and arbitrary weights.
-  c. scatter_rowscan_body_ns: lists of 1 .. 8193 ids (a partial chunk, exactly one, a chunk and one id, three chunks),
+  c. rowscan_sum: lists of 1 .. 8193 ids (a partial chunk, exactly one, a chunk and one id, three chunks),
      an id that straddles the chunk boundary, a hit list that has to flush, NS = 1, 2 and 4 at both ends, vocab % 4 != 0
      (dead waves at the barriers); scatter_rowscan_multi_kernel on ten unlike tables (the ninth opens a second launch).
   d. sort_id_positions: one, two and three passes of 8, 9 and 10 bits, each at both ends of its vocabulary range, a single

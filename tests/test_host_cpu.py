@@ -845,7 +845,7 @@ def test_hot_kernel_register_budgets(source, patterns, max_vgprs, agpr_spills_ok
     # the in-batch softmax's record packer (one 4-byte load per round trip, eight in a row at dim 64)
     ("softmax16.hip", "sm16_prep_kernelILi64E", 4),
     # the row-scan Adagrad of small tables (ids, gradient rows of a row's hits, accumulator / table rows)
-    ("embedding.hip", "scatter_rowscan_multi_kernel", 16),
+    ("sparse_update.hip", "scatter_rowscan_multi_kernel", 16),
     # the query prologue of the fp16 filter / threshold kernels: a wave's 16 x 16-byte query loads at once
     ("topk_scan16.hip", "scan16f_kernelILi64ELi16ELi2ELi2E", 8),
     ("topk_scan16.hip", "scan16_kernelILi64ELi2E", 8),

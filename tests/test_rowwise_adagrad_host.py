@@ -283,7 +283,7 @@ def test_new_kernels_use_no_scratch_and_do_not_spill():
   import tempfile
   from recommenders_amd.csrc import build as csrc_build
   found = {}
-  for source in ("embedding.hip", "table_update.hip"):
+  for source in ("sparse_update.hip", "table_update.hip"):
     src = os.path.join(os.path.dirname(csrc_build.__file__), source)
     out = os.path.join(tempfile.mkdtemp(prefix="tfrs_rowwise_"), source + ".s")
     subprocess.run([csrc_build.hipcc(), f"--offload-arch={csrc_build.ARCH}", "-O3", "-std=c++17",
@@ -299,5 +299,5 @@ def test_new_kernels_use_no_scratch_and_do_not_spill():
       assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0, name
       assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1)) == 0, name
       assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", block).group(1)) == 0, name
-  # embedding.hip: 2 learning-rate forms x (2 row-scan id types + 6 sorted forms); table_update.hip: 2 x 4 dense forms
-  assert found == {"embedding.hip": 16, "table_update.hip": 8}
+  # sparse_update.hip: 2 learning-rate forms x (2 row-scan id types + 6 sorted forms); table_update.hip: 2 x 4 dense forms
+  assert found == {"sparse_update.hip": 16, "table_update.hip": 8}

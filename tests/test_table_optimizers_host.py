@@ -336,7 +336,7 @@ def test_new_source_is_built():
   assert "table_update.hip" in csrc_build.SOURCES
 
 
-@pytest.mark.parametrize("source,expected", [("embedding.hip", 20), ("table_update.hip", 5)])
+@pytest.mark.parametrize("source,expected", [("sparse_update.hip", 20), ("table_update.hip", 5)])
 def test_table_update_kernels_use_no_scratch_and_do_not_spill(source, expected):
   """From the code object metadata of the cross-compiled source: every ``table_update_*`` kernel and the tick."""
   from recommenders_amd.csrc import build as csrc_build
@@ -356,6 +356,6 @@ def test_table_update_kernels_use_no_scratch_and_do_not_spill(source, expected):
     assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0, name
     assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1)) == 0, name
     assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", block).group(1)) == 0, name
-  # embedding.hip: 4 rules (Ftrl twice: sqrt and power 0) x (2 row-scan id types + 3 sorted forms);
+  # sparse_update.hip: 4 rules (Ftrl twice: sqrt and power 0) x (2 row-scan id types + 3 sorted forms);
   # table_update.hip: 4 dense kernels and the tick
   assert found == expected

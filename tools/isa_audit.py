@@ -5,7 +5,7 @@ loads in branches (`if (i < n) v = p[i]`): gfx950 counts a wave's loads with one
 cannot count loads issued under a condition and waits for every one ("Three code shapes").
 
   python tools/isa_audit.py                      # every source of recommenders_amd/csrc
-  python tools/isa_audit.py gemm16.hip embedding.hip --min-loads 8
+  python tools/isa_audit.py gemm16.hip sparse_update.hip --min-loads 8
 """
 import argparse, os, re, subprocess, sys, tempfile
 from collections import Counter
