@@ -660,6 +660,30 @@ int tfrs_logits_ce_bwd(const float *logits, const float *labels, int64_t nq, int
                        const float *grad_scale, float *dlogits, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Listwise ranking losses and NDCG on labels[nlists, len] / scores[nlists, len] (row-major f32), the losses and the
+ * metric that the listwise-ranking tutorial hands to tasks.Ranking (losses.py, metrics/listwise.py; formulas and
+ * summation orders: DESIGN 4.24 and the header of csrc/listwise.hip).  Position i of a list is valid iff
+ * labels[i] >= 0 (-1 pads); invalid positions are selected out, never multiplied by zero, and receive gradient +0.
+ * 1 <= len <= TFRS_LISTWISE_MAX_LEN and nlists * len < 2^31, else TFRS_EINVAL before any device call; nlists == 0
+ * returns TFRS_OK without a launch.  One launch each, on `stream`, no workspace, no atomics: bit-reproducible.
+ *   fwd:  loss[l] = the list's loss of `kind`
+ *   bwd:  dscores[l, i] = scale[l] * d loss[l] / d scores[l, i], recomputed from labels and scores alone
+ *   ndcg: ndcg[l] = DCG / IDCG over the first min(n, topn) ranks (topn == 0: no cut) and counted[l] = 1 where
+ *         IDCG > 0; else both 0
+ * ------------------------------------------------------------------------- */
+#define TFRS_LISTWISE_MAX_LEN 1024
+#define TFRS_LISTWISE_SOFTMAX 0
+#define TFRS_LISTWISE_PAIRWISE_LOGISTIC 1
+#define TFRS_LISTWISE_PAIRWISE_HINGE 2
+#define TFRS_LISTWISE_LIST_MLE 3
+int tfrs_listwise_loss_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len, float *loss,
+                           void *stream);
+int tfrs_listwise_loss_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                           const float *scale, float *dscores, void *stream);
+int tfrs_listwise_ndcg(const float *labels, const float *scores, int64_t nlists, int len, int topn, float *ndcg,
+                       float *counted, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Cross.call (layers/feature_interaction/dcn.py:151-186), full rank, linear
  * preactivation:  y = x0 * (x @ kernel + bias + diag_scale * x) + x
  * kernel[d, d] is Keras Dense layout [in, out]; bias may be NULL.

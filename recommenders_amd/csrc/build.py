@@ -41,6 +41,7 @@ SOURCES = [
     "softmax.hip",
     "softmax16.hip",
     "logits_ce.hip",
+    "listwise.hip",
     "interaction.hip",
     "gemm16.hip",
     "scann.hip",

@@ -1,0 +1,449 @@
+// listwise.hip -- listwise ranking losses (softmax, pairwise logistic, pairwise hinge, ListMLE) with their gradients,
+// and per-list NDCG, on [nlists, len] label / score matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24).
+//
+// Position i of a list is VALID iff label[i] >= 0 (-1 pads; a NaN label is not valid either).  Invalid positions are
+// selected out when the list is loaded -- their score is replaced by 0 and never enters any arithmetic -- and their
+// gradient is stored as +0.
+//
+// Work mapping.  A workgroup has 256 threads; a list belongs to a GROUP of G threads, G the smallest of
+// {8, 16, 32, 64} that is >= len, or 256 for 65 <= len <= 1024 (then a thread owns up to four items i = t + 256 c).
+// A workgroup therefore carries 32 / 16 / 8 / 4 / 1 lists: a 5-item list costs 8 lanes, not a workgroup.  A list lives
+// in the workgroup's LDS (scores, labels, 64-bit sort keys, two ping-pong scan buffers: 32 KiB at G = 256, 8 KiB below)
+// and in registers; nothing else is allocated, the backward recomputes everything from the two inputs.  Every loop
+// bound depends on (len, G) only -- never on the data -- so the workgroup barriers are uniform.
+//
+// Summation orders (every output is a fixed function of (kind, len); no atomics anywhere):
+//   group sum      a thread first adds its own items c = 0, 1, 2, 3 in that order; then a xor butterfly over the
+//                  min(G, 64) lanes of the group (offsets G/2, ..., 1); for G = 256 the four wave sums are added as
+//                  ((w0 + w1) + w2) + w3.
+//   pairwise       item i's loss / gradient contribution is the sum over j = 0, 1, ..., len - 1 in that order, in the
+//                  thread that owns i (so the contributions to one position are combined in one register); the
+//                  list's loss is the group sum of those.
+//   sort           bitonic network on P = the power of two >= len (>= G for G < 256) keys in LDS.  A key is
+//                  (orderable(value) << 32) | ~position, sorted descending: value descending, ties by position
+//                  ascending, a total order, so the result does not depend on the network.  Invalid slots hold key 0
+//                  and sink to the end.
+//   ListMLE        sorted by label.  lse_r (logsumexp of the scores at ranks >= r) is a Hillis-Steele suffix scan of
+//                  (max, sum) pairs, combine((m1, a1), (m2, a2)) = (m, a1 exp(m1 - m) + a2 exp(m2 - m)), m = max, with
+//                  distances 1, 2, 4, ... < P; the gradient's sum_{r <= t} exp(s_t - lse_r) = exp(s_t + q_t) with q_t the
+//                  same scan of -lse_r in the prefix direction.  Both scans never leave the range of the scores.
+//   softmax        max, sum of exp(s - max), sum of y (lse - s), sum of y: group sums.
+//   NDCG           two sorts (by score: DCG, by label: IDCG); each a group sum over the ranks r < min(n, topn) of
+//                  (2^y - 1) / log2(r + 2).
+#include "common.h"
+
+namespace tfrs {
+
+constexpr int kLwThreads = 256;
+constexpr int kLwMaxLen = TFRS_LISTWISE_MAX_LEN;
+enum { kLwSoftmax = TFRS_LISTWISE_SOFTMAX, kLwPairLogistic = TFRS_LISTWISE_PAIRWISE_LOGISTIC,
+       kLwPairHinge = TFRS_LISTWISE_PAIRWISE_HINGE, kLwListMle = TFRS_LISTWISE_LIST_MLE };
+
+template <int G>
+struct LwCfg {
+  static constexpr int IPT = G == 256 ? 4 : 1;   // items per thread
+  static constexpr int LPB = kLwThreads / G;     // lists per workgroup
+  static constexpr int CAP = G * IPT;            // LDS slots of one list
+  static constexpr int N = kLwThreads * IPT;     // LDS slots of the workgroup
+};
+
+template <int G>
+struct LwShared {
+  float s[LwCfg<G>::N];
+  float y[LwCfg<G>::N];
+  uint64_t key[LwCfg<G>::N];
+  float m[2][LwCfg<G>::N];
+  float a[2][LwCfg<G>::N];
+  float red[4];
+};
+
+template <int G>
+__device__ __forceinline__ float lw_sum(float v, float *red) {
+  constexpr int W = G < 64 ? G : 64;
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if constexpr (G == 256) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = ((red[0] + red[1]) + red[2]) + red[3];
+  }
+  return v;
+}
+template <int G>
+__device__ __forceinline__ float lw_max(float v, float *red) {
+  constexpr int W = G < 64 ? G : 64;
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  if constexpr (G == 256) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  }
+  return v;
+}
+
+// One list's view: registers of the owning threads + its LDS slots.
+template <int G>
+struct LwList {
+  int sub;          // thread within the group
+  int off;          // first LDS slot of the list
+  bool active;      // the group has a list
+  int64_t base;     // first element of the list in the matrices
+  float yv[LwCfg<G>::IPT], sv[LwCfg<G>::IPT];
+  bool valid[LwCfg<G>::IPT];
+};
+
+// Loads the list (invalid positions selected out: label -1, score 0) into registers and LDS; ends with a barrier.
+template <int G>
+__device__ __forceinline__ void lw_load(LwList<G> &l, LwShared<G> &sh, const float *__restrict__ labels,
+                                        const float *__restrict__ scores, int64_t nlists, int len) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  const int grp = threadIdx.x / G;
+  l.sub = threadIdx.x % G;
+  l.off = grp * LwCfg<G>::CAP;
+  const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + grp;
+  l.active = list < nlists;
+  l.base = list * len;
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) {
+    const int i = l.sub + G * c;
+    float y = -1.0f, s = 0.0f;
+    if (l.active && i < len) {
+      y = labels[l.base + i];
+      s = scores[l.base + i];
+    }
+    const bool v = y >= 0.0f;
+    l.valid[c] = v;
+    l.yv[c] = v ? y : -1.0f;
+    l.sv[c] = v ? s : 0.0f;
+    sh.y[l.off + i] = l.yv[c];
+    sh.s[l.off + i] = l.sv[c];
+  }
+  __syncthreads();
+}
+
+// Bitonic sort, descending, of the P keys of every list of the workgroup (P: power of two, G <= P or P <= CAP).
+template <int G>
+__device__ __forceinline__ void lw_sort(const LwList<G> &l, LwShared<G> &sh, int P) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  uint64_t *key = sh.key + l.off;
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int i = l.sub + G * c;
+        const int p = i ^ j;
+        if (i < P && p > i) {
+          const uint64_t a = key[i], b = key[p];
+          const bool desc = (i & k) == 0;
+          if (desc ? a < b : a > b) {
+            key[i] = b;
+            key[p] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ void lw_combine(float m1, float a1, float m2, float a2, float &m, float &a) {
+  m = fmaxf(m1, m2);
+  if (m == -__builtin_inff()) {
+    a = 0.0f;
+    return;
+  }
+  a = a1 * expf(m1 - m) + a2 * expf(m2 - m);
+}
+
+// Inclusive logsumexp scan of the (m, a) pairs in buffer 0 over P slots; SUFFIX: slot t combines t, t + 1, ...;
+// else t, t - 1, ....  Returns the buffer that holds the result.  Entry and exit: barrier done.
+template <int G, bool SUFFIX>
+__device__ __forceinline__ int lw_scan(const LwList<G> &l, LwShared<G> &sh, int P) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  int cur = 0;
+  for (int d = 1; d < P; d <<= 1) {
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int t = l.sub + G * c;
+      if (t < P) {
+        float m = sh.m[cur][l.off + t], a = sh.a[cur][l.off + t];
+        const int p = SUFFIX ? t + d : t - d;
+        if (p >= 0 && p < P) lw_combine(m, a, sh.m[cur][l.off + p], sh.a[cur][l.off + p], m, a);
+        sh.m[cur ^ 1][l.off + t] = m;
+        sh.a[cur ^ 1][l.off + t] = a;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  return cur;
+}
+
+__device__ __forceinline__ float lw_logistic(float x) { return fmaxf(-x, 0.0f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float lw_logistic_grad(float x) {      // -1 / (1 + exp(x)) without overflow
+  const float e = expf(-fabsf(x));
+  return x >= 0.0f ? -e / (1.0f + e) : -1.0f / (1.0f + e);
+}
+
+// Sum over j of item i's pair terms (see the header): loss terms, or gradient terms when BWD.
+template <int G, bool HINGE, bool BWD>
+__device__ __forceinline__ void lw_pairs(const LwList<G> &l, const LwShared<G> &sh, int len, float *acc) {
+  constexpr int IPT = LwCfg<G>::IPT;
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) acc[c] = 0.0f;
+  for (int j = 0; j < len; ++j) {
+    const float yj = sh.y[l.off + j], sj = sh.s[l.off + j];
+    if (!(yj >= 0.0f)) continue;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      if (!l.valid[c]) continue;
+      const float yi = l.yv[c], si = l.sv[c];
+      if (yi > yj) {
+        const float x = si - sj;
+        if (BWD) acc[c] += HINGE ? (x < 1.0f ? -1.0f : 0.0f) : lw_logistic_grad(x);
+        else acc[c] += HINGE ? fmaxf(0.0f, 1.0f - x) : lw_logistic(x);
+      } else if (BWD && yj > yi) {
+        const float x = sj - si;
+        acc[c] -= HINGE ? (x < 1.0f ? -1.0f : 0.0f) : lw_logistic_grad(x);
+      }
+    }
+  }
+}
+
+template <int G, bool BWD>
+__global__ void __launch_bounds__(kLwThreads) listwise_loss_kernel(int kind, const float *__restrict__ labels,
+                                                                   const float *__restrict__ scores, int64_t nlists,
+                                                                   int len, int P, const float *__restrict__ scale,
+                                                                   float *__restrict__ out) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  __shared__ LwShared<G> sh;
+  LwList<G> l;
+  lw_load<G>(l, sh, labels, scores, nlists, len);
+  const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
+  const float sc = (BWD && l.active) ? scale[list] : 0.0f;
+  float g[IPT];        // BWD: gradient of the item a thread owns (softmax, pairwise)
+  float loss = 0.0f;   // !BWD: the list's loss
+
+  if (kind == kLwSoftmax) {
+    float t = -__builtin_inff();
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) if (l.valid[c]) t = fmaxf(t, l.sv[c]);
+    const float mx = lw_max<G>(t, sh.red);
+    t = 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) if (l.valid[c]) t += expf(l.sv[c] - mx);
+    const float se = lw_sum<G>(t, sh.red);
+    const float lse = mx + logf(se);                // n == 0: no valid item below reads it
+    t = 0.0f;
+    if (BWD) {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (l.valid[c]) t += l.yv[c];
+      const float ysum = lw_sum<G>(t, sh.red);
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) g[c] = l.valid[c] ? ysum * expf(l.sv[c] - lse) - l.yv[c] : 0.0f;
+    } else {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (l.valid[c]) t += l.yv[c] * (lse - l.sv[c]);
+      loss = lw_sum<G>(t, sh.red);
+    }
+  } else if (kind == kLwPairLogistic || kind == kLwPairHinge) {
+    float acc[IPT];
+    if (kind == kLwPairHinge) lw_pairs<G, true, BWD>(l, sh, len, acc);
+    else lw_pairs<G, false, BWD>(l, sh, len, acc);
+    if (BWD) {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) g[c] = acc[c];
+    } else {
+      float t = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) t += acc[c];
+      loss = lw_sum<G>(t, sh.red);
+    }
+  } else {   // ListMLE
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      sh.key[l.off + i] = l.valid[c] ? make_key(l.yv[c], i) : 0ull;
+    }
+    __syncthreads();
+    lw_sort<G>(l, sh, P);
+    int pos[IPT];
+    bool ok[IPT];
+    float sp[IPT], lse[IPT];
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int t = l.sub + G * c;
+      const uint64_t k = t < P ? sh.key[l.off + t] : 0ull;
+      ok[c] = k != 0ull;
+      pos[c] = ok[c] ? key_index(k) : 0;
+      sp[c] = ok[c] ? sh.s[l.off + pos[c]] : 0.0f;
+      if (t < P) {
+        sh.m[0][l.off + t] = ok[c] ? sp[c] : -__builtin_inff();
+        sh.a[0][l.off + t] = ok[c] ? 1.0f : 0.0f;
+      }
+    }
+    __syncthreads();
+    int buf = lw_scan<G, true>(l, sh, P);
+    float t = 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int r = l.sub + G * c;
+      lse[c] = ok[c] ? sh.m[buf][l.off + r] + logf(sh.a[buf][l.off + r]) : 0.0f;
+      if (ok[c]) t += lse[c] - sp[c];
+    }
+    if (!BWD) {
+      loss = lw_sum<G>(t, sh.red);
+    } else {
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int r = l.sub + G * c;
+        if (r < P) {
+          sh.m[0][l.off + r] = ok[c] ? -lse[c] : -__builtin_inff();
+          sh.a[0][l.off + r] = ok[c] ? 1.0f : 0.0f;
+        }
+      }
+      __syncthreads();
+      buf = lw_scan<G, false>(l, sh, P);
+      // padded positions first (+0), then every valid item at its own position: disjoint
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int i = l.sub + G * c;
+        if (l.active && i < len && !l.valid[c]) out[l.base + i] = 0.0f;
+      }
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int r = l.sub + G * c;
+        if (l.active && ok[c]) {
+          const float q = sh.m[buf][l.off + r] + logf(sh.a[buf][l.off + r]);
+          out[l.base + pos[c]] = sc * (expf(sp[c] + q) - 1.0f);
+        }
+      }
+    }
+    if (BWD) return;
+  }
+
+  if (BWD) {
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      if (l.active && i < len) out[l.base + i] = l.valid[c] ? sc * g[c] : 0.0f;
+    }
+  } else if (l.active && l.sub == 0) {
+    out[list] = loss;
+  }
+}
+
+template <int G>
+__global__ void __launch_bounds__(kLwThreads) listwise_ndcg_kernel(const float *__restrict__ labels,
+                                                                   const float *__restrict__ scores, int64_t nlists,
+                                                                   int len, int P, int topn, float *__restrict__ ndcg,
+                                                                   float *__restrict__ counted) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  __shared__ LwShared<G> sh;
+  LwList<G> l;
+  lw_load<G>(l, sh, labels, scores, nlists, len);
+  const int lim = topn > 0 && topn < P ? topn : P;
+  float sums[2];
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {   // 0: by score (DCG), 1: by label (IDCG)
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      sh.key[l.off + i] = l.valid[c] ? make_key(pass == 0 ? l.sv[c] : l.yv[c], i) : 0ull;
+    }
+    __syncthreads();
+    lw_sort<G>(l, sh, P);
+    float t = 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int r = l.sub + G * c;
+      const uint64_t k = r < lim ? sh.key[l.off + r] : 0ull;
+      if (k != 0ull) t += (exp2f(sh.y[l.off + key_index(k)]) - 1.0f) / log2f((float)(r + 2));
+    }
+    sums[pass] = lw_sum<G>(t, sh.red);
+    __syncthreads();
+  }
+  if (l.active && l.sub == 0) {
+    const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
+    const bool cnt = sums[1] > 0.0f;
+    ndcg[list] = cnt ? sums[0] / sums[1] : 0.0f;
+    counted[list] = cnt ? 1.0f : 0.0f;
+  }
+}
+
+static int lw_group(int len) { return len <= 8 ? 8 : len <= 16 ? 16 : len <= 32 ? 32 : len <= 64 ? 64 : 256; }
+static int lw_pow2(int len, int g) {
+  int p = g < 256 ? g : 128;
+  while (p < len) p <<= 1;
+  return p;
+}
+
+static int lw_check_shape(const char *what, int64_t nlists, int len) {
+  TFRS_CHECK_ARG(nlists >= 0, "%s: nlists must be non-negative", what);
+  TFRS_CHECK_ARG(len >= 1 && len <= kLwMaxLen, "%s: len=%d outside 1 .. %d", what, len, kLwMaxLen);
+  TFRS_CHECK_ARG(nlists * (int64_t)len < (1ll << 31), "%s: nlists * len must stay below 2^31", what);
+  return TFRS_OK;
+}
+
+#define TFRS_LW_DISPATCH(KERNEL, ...)                                                                       \
+  do {                                                                                                      \
+    const int g_ = lw_group(len);                                                                           \
+    const int P = lw_pow2(len, g_);                                                                         \
+    const unsigned grid_ = (unsigned)((nlists + (kLwThreads / g_) - 1) / (kLwThreads / g_));                \
+    switch (g_) {                                                                                           \
+      case 8: hipLaunchKernelGGL((KERNEL(8)), dim3(grid_), dim3(kLwThreads), 0, s, __VA_ARGS__); break;     \
+      case 16: hipLaunchKernelGGL((KERNEL(16)), dim3(grid_), dim3(kLwThreads), 0, s, __VA_ARGS__); break;   \
+      case 32: hipLaunchKernelGGL((KERNEL(32)), dim3(grid_), dim3(kLwThreads), 0, s, __VA_ARGS__); break;   \
+      case 64: hipLaunchKernelGGL((KERNEL(64)), dim3(grid_), dim3(kLwThreads), 0, s, __VA_ARGS__); break;   \
+      default: hipLaunchKernelGGL((KERNEL(256)), dim3(grid_), dim3(kLwThreads), 0, s, __VA_ARGS__); break;  \
+    }                                                                                                       \
+  } while (0)
+
+#define TFRS_LW_FWD(G) listwise_loss_kernel<G, false>
+#define TFRS_LW_BWD(G) listwise_loss_kernel<G, true>
+#define TFRS_LW_NDCG(G) listwise_ndcg_kernel<G>
+
+}  // namespace tfrs
+
+using namespace tfrs;
+
+extern "C" int tfrs_listwise_loss_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                      float *loss, void *stream) {
+  TFRS_CHECK_ARG(kind >= kLwSoftmax && kind <= kLwListMle, "listwise_loss_fwd: unknown kind %d", kind);
+  if (int rc = lw_check_shape("listwise_loss_fwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && loss, "listwise_loss_fwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const float *no_scale = nullptr;
+  TFRS_LW_DISPATCH(TFRS_LW_FWD, kind, labels, scores, nlists, len, P, no_scale, loss);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_loss_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                      const float *scale, float *dscores, void *stream) {
+  TFRS_CHECK_ARG(kind >= kLwSoftmax && kind <= kLwListMle, "listwise_loss_bwd: unknown kind %d", kind);
+  if (int rc = lw_check_shape("listwise_loss_bwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && scale && dscores, "listwise_loss_bwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  TFRS_LW_DISPATCH(TFRS_LW_BWD, kind, labels, scores, nlists, len, P, scale, dscores);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_ndcg(const float *labels, const float *scores, int64_t nlists, int len, int topn,
+                                  float *ndcg, float *counted, void *stream) {
+  TFRS_CHECK_ARG(topn >= 0, "listwise_ndcg: topn=%d must be positive, or 0 for no cut", topn);
+  if (int rc = lw_check_shape("listwise_ndcg", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && ndcg && counted, "listwise_ndcg: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  TFRS_LW_DISPATCH(TFRS_LW_NDCG, labels, scores, nlists, len, P, topn, ndcg, counted);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}

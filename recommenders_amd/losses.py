@@ -64,3 +64,109 @@ class MeanSquaredError(_Loss):
   def _per_sample(self, y_true, y_pred):
     se = (y_pred - y_true) ** 2
     return se.mean(dim=-1) if se.dim() > 1 else se
+
+
+# ------------------------------------------------------------------------------------------------
+# Listwise ranking losses: y_true / y_pred are [batch, list]; a position is valid iff
+# y_true >= 0 (-1 pads, TF-Ranking's convention).  One fused HIP kernel per direction
+# (csrc/listwise.hip): a list lives in LDS and registers, no [B, L, L] tensor exists, the backward
+# recomputes from the two inputs.  sample_weight is PER LIST ([B] or [B, 1]).
+# ------------------------------------------------------------------------------------------------
+MAX_LIST_LEN = 1024
+_SOFTMAX, _PAIRWISE_LOGISTIC, _PAIRWISE_HINGE, _LIST_MLE = 0, 1, 2, 3
+
+
+def _listwise_inputs(y_true: torch.Tensor, y_pred: torch.Tensor, what: str, sample_weight=None):
+  """float32, contiguous, rank 2, on the GPU, inside the kernels' envelope; every shape is checked before the device."""
+  if not isinstance(y_pred, torch.Tensor) or not isinstance(y_true, torch.Tensor):
+    raise ValueError(f"{what}: y_true and y_pred must be tensors")
+  if y_pred.dim() != 2 or y_true.dim() != 2 or y_true.shape != y_pred.shape:
+    raise ValueError(f"{what}: y_true and y_pred must both be [batch, list], got {tuple(y_true.shape)} and "
+                     f"{tuple(y_pred.shape)}")
+  b, l = y_pred.shape
+  if not 1 <= l <= MAX_LIST_LEN:
+    raise ValueError(f"{what}: list length {l} outside 1 .. MAX_LIST_LEN = {MAX_LIST_LEN}")
+  if b * l >= 2 ** 31:
+    raise ValueError(f"{what}: batch * list length = {b * l} must stay below 2^31")
+  if sample_weight is not None and tuple(torch.as_tensor(sample_weight).shape) not in ((b,), (b, 1)):
+    raise ValueError(f"{what}: sample_weight is per list, [{b}] or [{b}, 1]; got "
+                     f"{tuple(torch.as_tensor(sample_weight).shape)}")
+  if not y_pred.is_cuda:
+    raise RuntimeError(f"{what} needs its inputs on the GPU (device={y_pred.device}); there is no CPU fallback")
+  y_pred = y_pred.to(torch.float32).contiguous()
+  y_true = y_true.to(y_pred.device, torch.float32).contiguous()
+  return y_true, y_pred
+
+
+class _ListwiseFn(torch.autograd.Function):
+  """Per-list loss ``[B]`` of one kind over ``tfrs_listwise_loss_fwd`` / ``_bwd``; only the two inputs are kept."""
+
+  @staticmethod
+  def forward(ctx, y_pred, y_true, kind):
+    from recommenders_amd import _lib
+    b, l = y_pred.shape
+    loss = torch.empty((b,), dtype=torch.float32, device=y_pred.device)
+    _lib.check(_lib.load().tfrs_listwise_loss_fwd(kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l, _lib.ptr(loss),
+                                                   _lib.current_stream()))
+    ctx.save_for_backward(y_true, y_pred)
+    ctx.kind = kind
+    return loss
+
+  @staticmethod
+  def backward(ctx, grad):
+    from recommenders_amd import _lib
+    y_true, y_pred = ctx.saved_tensors
+    b, l = y_pred.shape
+    scale = grad.to(torch.float32).contiguous()      # [B]: upstream gradient x list weight x reduction factor
+    ds = torch.empty_like(y_pred)
+    _lib.check(_lib.load().tfrs_listwise_loss_bwd(ctx.kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l,
+                                                   _lib.ptr(scale), _lib.ptr(ds), _lib.current_stream()))
+    return ds, None, None
+
+
+class _ListwiseLoss(_Loss):
+  _KIND = None
+
+  def _per_sample(self, y_true, y_pred):
+    return _ListwiseFn.apply(y_pred, y_true, self._KIND)
+
+  def __call__(self, y_true, y_pred, sample_weight=None) -> torch.Tensor:
+    y_true, y_pred = _listwise_inputs(y_true, y_pred, type(self).__name__, sample_weight)
+    if y_pred.shape[0] == 0:                         # no launch: an empty vector, or a zero that still back-propagates
+      return y_pred.sum(dim=-1) if self.reduction == "none" else y_pred.sum()
+    if sample_weight is not None:
+      sample_weight = torch.as_tensor(sample_weight)
+    return super().__call__(y_true, y_pred, sample_weight)
+
+
+class SoftmaxLoss(_ListwiseLoss):
+  """``sum_i y_i (logsumexp(s) - s_i)`` over the valid items of a list."""
+  _KIND = _SOFTMAX
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "softmax_loss"):
+    super().__init__(reduction, name)
+
+
+class PairwiseLogisticLoss(_ListwiseLoss):
+  """``sum_{y_i > y_j} log(1 + exp(-(s_i - s_j)))`` over the valid pairs of a list."""
+  _KIND = _PAIRWISE_LOGISTIC
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_logistic_loss"):
+    super().__init__(reduction, name)
+
+
+class PairwiseHingeLoss(_ListwiseLoss):
+  """``sum_{y_i > y_j} max(0, 1 - (s_i - s_j))`` over the valid pairs of a list."""
+  _KIND = _PAIRWISE_HINGE
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_hinge_loss"):
+    super().__init__(reduction, name)
+
+
+class ListMLELoss(_ListwiseLoss):
+  """Negative Plackett-Luce log-likelihood of the label order (label descending, ties by position ascending:
+  deterministic, where TF-Ranking shuffles ties)."""
+  _KIND = _LIST_MLE
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "list_mle_loss"):
+    super().__init__(reduction, name)

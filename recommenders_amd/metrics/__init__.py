@@ -2,3 +2,4 @@
 
 from recommenders_amd.metrics.factorized_top_k import Factorized, FactorizedTopK, Mean  # noqa: F401
 from recommenders_amd.metrics.basic import AUC, BinaryAccuracy, RootMeanSquaredError  # noqa: F401
+from recommenders_amd.metrics.listwise import NDCGMetric  # noqa: F401

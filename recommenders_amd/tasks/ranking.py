@@ -1,7 +1,12 @@
 """The ranking task (mirror of ``tensorflow_recommenders/tasks/ranking.py:26-119``): same
 constructor and ``call`` arguments.  ``loss`` defaults to binary cross-entropy (:60-61);
 ``metrics`` see ``(y_true, y_pred)``, ``prediction_metrics`` the predictions,
-``label_metrics`` the labels, ``loss_metrics`` the already-reduced loss (:97-110)."""
+``label_metrics`` the labels, ``loss_metrics`` the already-reduced loss (:97-110).
+
+Listwise ranking (the reference's listwise tutorial) needs nothing else from the task: with ``labels`` and
+``predictions`` of shape ``[batch, list]`` (``-1`` labels pad a list) pass ``loss=losses.SoftmaxLoss()``,
+``PairwiseLogisticLoss()``, ``PairwiseHingeLoss()`` or ``ListMLELoss()`` and ``metrics=[metrics.NDCGMetric(topn=...)]``;
+``sample_weight`` is then one weight per list."""
 
 from typing import Callable, List, Optional
 
