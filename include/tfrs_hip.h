@@ -325,6 +325,11 @@ int tfrs_rank_count_accumulate(const float *queries, const float *true_candidate
 int tfrs_topk_hits_update(uint32_t *counts, int64_t nq, const int32_t *ks_h, int nks,
                           const float *sample_weight, float *state, float *results, float *hits,
                           void *stream);
+/* The split geometry of tfrs_rank_count_accumulate at (nq, nc, d), from the function the launch
+ * calls (host only, no device work): out = [n_qtiles (128-query tiles), tiles_per_split (32-row
+ * candidate tiles per workgroup), nsplits, max_tiles (the LDS bound on tiles_per_split)].
+ * TFRS_EINVAL for nq < 1, nc < 1, d outside [1, 128] or a NULL out. */
+int tfrs_rank_count_plan(int64_t nq, int64_t nc, int d, int64_t *out);
 
 /* ------------------------------------------------------------------------- *
  * Embedding lookup (tf.keras.layers.Embedding as called at README.md:62-66,77-78;

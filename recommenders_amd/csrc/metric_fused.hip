@@ -358,6 +358,28 @@ static void launch_rank_count(const RankCountArgs &a, int nsplits, hipStream_t s
   hipLaunchKernelGGL((rank_count_kernel<DP>), dim3((unsigned)(nsplits * a.n_qtiles)), dim3(256), 0, s, a);
 }
 
+// The split geometry of one launch (host only): what tfrs_rank_count_accumulate launches and what
+// tfrs_rank_count_plan reports.
+struct RankPlan {
+  int64_t n_qtiles, tiles_per_split, nsplits, max_tiles;
+};
+
+static RankPlan rank_count_plan(int64_t nq, int64_t nc, int d) {
+  RankPlan p;
+  p.n_qtiles = (nq + 127) / 128;
+  p.max_tiles = padded_dim(d) <= 64 ? 7 : 3;
+  const int64_t ntiles = (nc + 31) / 32;
+  // One workgroup per CU where the problem allows it: the launch is bound by the f32 matrix pipe
+  // (64 cycles per 32x32x2 step), so what matters is that every SIMD gets the same number of
+  // wave-tiles -- 256 workgroups x 4 waves put exactly one wave on each of the 1024 SIMDs (at the
+  // quickstart shapes 7 tiles each against 6.6 ideal) -- and that each workgroup pays its load
+  // latencies once.  At most max_tiles tiles per workgroup (LDS).
+  const int64_t want_splits = std::max<int64_t>(1, 256 / p.n_qtiles);
+  p.tiles_per_split = std::min<int64_t>(p.max_tiles, std::max<int64_t>(1, (ntiles + want_splits - 1) / want_splits));
+  p.nsplits = (ntiles + p.tiles_per_split - 1) / p.tiles_per_split;
+  return p;
+}
+
 }  // namespace tfrs
 
 extern "C" int tfrs_rank_count_accumulate(const float *queries, const float *true_candidates, int64_t nq,
@@ -376,30 +398,31 @@ extern "C" int tfrs_rank_count_accumulate(const float *queries, const float *tru
   RankCountArgs a;
   a.q = queries; a.true_c = true_candidates; a.nq = nq; a.d = d; a.cand = candidates; a.ids = cand_ids;
   a.ids_i64 = ids_i64; a.nc = nc; a.vocab = vocab; a.counts = counts; a.mark_nonfinite = first_block ? 1 : 0;
-  a.n_qtiles = (int)((nq + 127) / 128);
-  const int dp = padded_dim(d);
-  const int max_tiles = dp <= 64 ? 7 : 3;
-  const int64_t ntiles = (nc + 31) / 32;
-  // One workgroup per CU where the problem allows it: the launch is bound by the f32 matrix pipe
-  // (64 cycles per 32x32x2 step), so what matters is that every SIMD gets the same number of
-  // wave-tiles -- 256 workgroups x 4 waves put exactly one wave on each of the 1024 SIMDs (at the
-  // quickstart shapes 7 tiles each against 6.6 ideal) -- and that each workgroup pays its load
-  // latencies once.  At most max_tiles tiles per workgroup (LDS).
-  int64_t want_splits = std::max<int64_t>(1, 256 / a.n_qtiles);
-  int64_t tps = std::min<int64_t>(max_tiles, std::max<int64_t>(1, (ntiles + want_splits - 1) / want_splits));
-  const int64_t nsplits = (ntiles + tps - 1) / tps;
-  TFRS_CHECK_ARG(nsplits * a.n_qtiles <= 0x7FFFFFFF, "rank_count: grid too large (%lld x %d workgroups)",
-                 (long long)nsplits, a.n_qtiles);
-  a.tiles_per_split = (int)tps;
+  const RankPlan p = rank_count_plan(nq, nc, d);
+  TFRS_CHECK_ARG(p.nsplits * p.n_qtiles <= 0x7FFFFFFF, "rank_count: grid too large (%lld x %lld workgroups)",
+                 (long long)p.nsplits, (long long)p.n_qtiles);
+  a.n_qtiles = (int)p.n_qtiles;                 // (both fit an int: their product does)
+  a.tiles_per_split = (int)p.tiles_per_split;
+  const int nsplits = (int)p.nsplits;
   hipStream_t s = (hipStream_t)stream;
-  switch (dp) {
-    case 8: launch_rank_count<8>(a, (int)nsplits, s); break;
-    case 16: launch_rank_count<16>(a, (int)nsplits, s); break;
-    case 32: launch_rank_count<32>(a, (int)nsplits, s); break;
-    case 64: launch_rank_count<64>(a, (int)nsplits, s); break;
-    default: launch_rank_count<128>(a, (int)nsplits, s); break;
+  switch (padded_dim(d)) {
+    case 8: launch_rank_count<8>(a, nsplits, s); break;
+    case 16: launch_rank_count<16>(a, nsplits, s); break;
+    case 32: launch_rank_count<32>(a, nsplits, s); break;
+    case 64: launch_rank_count<64>(a, nsplits, s); break;
+    default: launch_rank_count<128>(a, nsplits, s); break;
   }
   TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+// The split geometry of tfrs_rank_count_accumulate at (nq, nc, d) (host only, no device call):
+// out = [n_qtiles, tiles_per_split, nsplits, max_tiles].
+extern "C" int tfrs_rank_count_plan(int64_t nq, int64_t nc, int d, int64_t *out) {
+  using namespace tfrs;
+  TFRS_CHECK_ARG(nq >= 1 && nc >= 1 && d >= 1 && d <= 128 && out, "rank_count_plan: bad argument");
+  const RankPlan p = rank_count_plan(nq, nc, d);
+  out[0] = p.n_qtiles; out[1] = p.tiles_per_split; out[2] = p.nsplits; out[3] = p.max_tiles;
   return TFRS_OK;
 }
 

@@ -241,7 +241,8 @@ class FactorizedTopK(Factorized):
           _lib.check(lib.tfrs_rank_count_accumulate(
               _lib.ptr(q), _lib.ptr(c), nq, d, _lib.ptr(block), None, 0, block.shape[0],
               block.shape[0], _lib.ptr(counts), first, stream))
-          first = 0
+          if block.shape[0] > 0:          # (an empty block launches nothing: the next one still flags the non-finite positives)
+            first = 0
       _lib.check(lib.tfrs_topk_hits_update(
           _lib.ptr(counts), nq, ks_arr, len(self._ks), _lib.ptr(w), _lib.ptr(state),
           _lib.ptr(results), None, stream))
