@@ -795,6 +795,34 @@ int tfrs_cross_fwd_f16(const float *x0, const float *x, const float *kernel, con
                        float diag_scale, int64_t batch, int d, float *y, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* What the GEMM launchers would choose for the product C[m, n] = A[m, k] @ B[k, n], answered by the functions
+ * the launchers themselves call.  Host only, no device work (the layout tests ask it which kernel, which operand
+ * preparation and which K slices a shape reaches).  f16: 0 = the f32 MFMA kernel, 1 = the split-fp16 GEMM (which
+ * reads TFRS_GEMM16_TILE / TFRS_GEMM16_SPLITK like its launcher).
+ *   flags   TFRS_GEMM_PLAN_AT / _BT: the array holds the transpose of A ([k, m]) / of B ([n, k]);
+ *           _AMUL / _BMUL: the operand has a fused element-wise multiplier; _EPI: a Cross-type epilogue;
+ *           _BIAS: a bias; _ACT: an activation or a pre-activation output.
+ *   align   the low four address bits of a | b << 4 | a's multiplier << 8 | b's multiplier << 12.
+ *   out     int64[20].  f16 = 1:
+ *           [0] 1 = 256 x 256 kernel, 0 = 128 x 128   [1] kp  [2] mp  [3] np  [4] K block of the images (16 or kp)
+ *           [5] 256-row slabs of the column pass  [6] slices asked for  [7] K steps of 16 per slice (0: no split)
+ *           [8] non-empty slices  [9] K steps of the last slice
+ *           [10..14] operand A, [15..19] operand B: kind (0 row-per-wave kernel, 1 column-maximum + column pass,
+ *           2 single-pass K-step-major rows, 3 two-pass K-step-major rows), register steps, 8-byte-load form,
+ *           waves per four rows (kind 2 only), 16-byte loads (kinds 0, 1, 3).
+ *           f16 = 0 (the A^T B product is the one that splits; A^T B^T does not exist: TFRS_EINVAL):
+ *           [0] slices asked for  [1] K rows per slice (0: no split)  [2] non-empty slices  [3] K rows of the last
+ *           slice  [4] / [5] 16-byte loads of A / B  [6] 128 x 128 output tiles.
+ * m, n, k < 1 or an unknown flag: TFRS_EINVAL. */
+#define TFRS_GEMM_PLAN_AT 1
+#define TFRS_GEMM_PLAN_BT 2
+#define TFRS_GEMM_PLAN_AMUL 4
+#define TFRS_GEMM_PLAN_BMUL 8
+#define TFRS_GEMM_PLAN_EPI 16
+#define TFRS_GEMM_PLAN_BIAS 32
+#define TFRS_GEMM_PLAN_ACT 64
+int tfrs_gemm_plan(int f16, int64_t m, int n, int64_t k, int flags, int align, int64_t *out);
+
 /* ------------------------------------------------------------------------- *
  * Row-sharded embedding lookup, owner bucketing (the multi-device
  * embedding of the reference is TPUEmbedding, layers/embedding/tpu_embedding_layer.py:699-720):

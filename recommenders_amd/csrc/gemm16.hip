@@ -62,6 +62,12 @@ __device__ __forceinline__ int64_t g16_img_off(int64_t row, int k, int kp, int k
   return kb == kp ? row * (int64_t)kp + k : ((int64_t)(k / kb) * rows_p + row) * kb + (k % kb);
 }
 
+// 16-byte loads of an operand (and its multiplier, 0 = none): rows of `ld` floats stay 16-byte aligned.  One
+// predicate for the prep kernels and for tfrs_gemm_plan (which passes the low address bits only).
+__host__ __device__ __forceinline__ bool g16_vec_ok(int64_t ld, uintptr_t p, uintptr_t mul) {
+  return (ld % 4 == 0) && ((p & 15) == 0) && ((mul & 15) == 0);
+}
+
 // ---- prep: rows of A ------------------------------------------------------------------------
 // one wave per row; rows in [m, mp) and columns in [k, kp) are zero
 // `mul` (optional, same shape as x): the image is built from x * mul (dz = dy * x0 of the Cross
@@ -82,8 +88,7 @@ __global__ void __launch_bounds__(256) g16_prep_rows_kernel(const float *__restr
   const bool valid = row < m;
   const float *xr = x + row * (int64_t)k;
   const float *mr = mul ? mul + row * (int64_t)k : nullptr;
-  const bool vec = (k % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                   (!mul || (reinterpret_cast<uintptr_t>(mul) & 15) == 0);
+  const bool vec = g16_vec_ok(k, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(mul));
   float mx = 0.0f;
   if (valid) {
     if (vec) {
@@ -145,8 +150,7 @@ __global__ void __launch_bounds__(256) g16_prep_rows_ksm_kernel(const float *__r
   const bool valid = row < m;
   const float *xr = x + row * (int64_t)k;
   const float *mr = mul ? mul + row * (int64_t)k : nullptr;
-  const bool vec = (k % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                   (!mul || (reinterpret_cast<uintptr_t>(mul) & 15) == 0);
+  const bool vec = g16_vec_ok(k, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(mul));
   auto load4 = [&](int c, float (&v)[4]) __attribute__((always_inline)) {
     v[0] = v[1] = v[2] = v[3] = 0.0f;
     if (!valid) return;
@@ -286,32 +290,48 @@ __global__ void __launch_bounds__(NW * 64) g16_prep_rows_ksm1_kernel(const float
   }
 }
 
+// Which row-prep kernel builds a K-step-major image of rows of k floats: the single-pass kernel with `steps` register
+// steps per lane (`v2`: the 8-byte-load form, on `waves` waves per four rows), or, steps == 0, the two-pass kernel.
+// x_low / mul_low: the low address bits of the operand and of its multiplier (0 without one).  The launcher below and
+// tfrs_gemm_plan both ask this function.
+struct G16RowPrep {
+  int steps;
+  bool v2;
+  int waves;
+};
+static G16RowPrep g16_row_prep(int k, int kp, uintptr_t x_low, uintptr_t mul_low) {
+  const int nq4 = (kp / 16 + 3) / 4, steps = (nq4 + 7) / 8;
+  const bool vec = k >= 4 && g16_vec_ok(k, x_low, mul_low);
+  // 8-byte aligned rows (k % 4 == 2): the same single-pass kernel with 8-byte loads
+  const bool vec2 = !vec && (k % 4 == 2) && k >= 6 && ((x_low & 7) == 0) && ((mul_low & 7) == 0);
+  if (vec2 && steps <= 4) return {4, true, 4};
+  if (vec2 && steps <= 16) return {8, true, 8};    // (eight waves per four rows: eight steps per lane)
+  if (vec && steps <= 2) return {2, false, 4};
+  if (vec && steps <= 4) return {4, false, 4};
+  if (vec && steps <= 8) return {8, false, 4};
+  if (vec && steps <= 16) return {16, false, 4};   // kp <= 8192 (DLRM top MLP: 5082)
+  return {0, false, 4};
+}
+
 static void g16_launch_prep_rows_ksm(const float *x, const float *mul, int64_t m, int k, int kp, _Float16 *hi,
                                      _Float16 *lo, float *inv, int64_t rows_p, hipStream_t s) {
-  const int nq4 = (kp / 16 + 3) / 4, steps = (nq4 + 7) / 8;
   const dim3 grid1((unsigned)(rows_p / 4));
-  const bool vec = (k % 4 == 0) && k >= 4 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                   (!mul || (reinterpret_cast<uintptr_t>(mul) & 15) == 0);
-  // 8-byte aligned rows (k % 4 == 2): the same single-pass kernel with 8-byte loads
-  const bool vec2 = !vec && (k % 4 == 2) && k >= 6 && ((reinterpret_cast<uintptr_t>(x) & 7) == 0) &&
-                    (!mul || (reinterpret_cast<uintptr_t>(mul) & 7) == 0);
-#define TFRS_KSM1V2(S, M) \
-  hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<S, M, true>), grid1, dim3(256), 0, s, x, mul, m, k, kp, hi, lo, inv, rows_p)
-  if (vec2 && steps <= 4) { if (mul) TFRS_KSM1V2(4, true); else TFRS_KSM1V2(4, false); return; }
-  if (vec2 && steps <= 16) {    // (eight waves per four rows: eight steps per lane)
-    if (mul)
-      hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<8, true, true, 8>), grid1, dim3(512), 0, s, x, mul, m, k, kp, hi, lo, inv, rows_p);
-    else
-      hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<8, false, true, 8>), grid1, dim3(512), 0, s, x, mul, m, k, kp, hi, lo, inv, rows_p);
-    return;
-  }
-#undef TFRS_KSM1V2
-#define TFRS_KSM1(S, M) \
-  hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<S, M>), grid1, dim3(256), 0, s, x, mul, m, k, kp, hi, lo, inv, rows_p)
-  if (vec && steps <= 2) { if (mul) TFRS_KSM1(2, true); else TFRS_KSM1(2, false); }
-  else if (vec && steps <= 4) { if (mul) TFRS_KSM1(4, true); else TFRS_KSM1(4, false); }
-  else if (vec && steps <= 8) { if (mul) TFRS_KSM1(8, true); else TFRS_KSM1(8, false); }
-  else if (vec && steps <= 16) { if (mul) TFRS_KSM1(16, true); else TFRS_KSM1(16, false); }   // kp <= 8192 (DLRM top MLP: 5082)
+  const G16RowPrep v = g16_row_prep(k, kp, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(mul));
+#define TFRS_KSM1(S, V2, NW)                                                                                          \
+  do {                                                                                                                \
+    if (mul)                                                                                                          \
+      hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<S, true, V2, NW>), grid1, dim3(NW * 64), 0, s, x, mul, m, k, kp, hi, \
+                         lo, inv, rows_p);                                                                            \
+    else                                                                                                              \
+      hipLaunchKernelGGL((g16_prep_rows_ksm1_kernel<S, false, V2, NW>), grid1, dim3(NW * 64), 0, s, x, mul, m, k, kp, hi, \
+                         lo, inv, rows_p);                                                                            \
+  } while (0)
+  if (v.v2 && v.waves == 4) TFRS_KSM1(4, true, 4);
+  else if (v.v2) TFRS_KSM1(8, true, 8);
+  else if (v.steps == 2) TFRS_KSM1(2, false, 4);
+  else if (v.steps == 4) TFRS_KSM1(4, false, 4);
+  else if (v.steps == 8) TFRS_KSM1(8, false, 4);
+  else if (v.steps == 16) TFRS_KSM1(16, false, 4);
 #undef TFRS_KSM1
   else
     hipLaunchKernelGGL(g16_prep_rows_ksm_kernel, dim3((unsigned)(rows_p / 16)), dim3(256), 0, s, x, mul, m, k, kp, hi,
@@ -421,8 +441,7 @@ __global__ void __launch_bounds__(256) g16_prep_cols_kernel(const float *__restr
     s_scale[tid] = s;
     if (blockIdx.y == 0) inv[n0 + tid] = iv;
   }
-  const bool vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(b) & 15) == 0) &&
-                   (!mul || (reinterpret_cast<uintptr_t>(mul) & 15) == 0);
+  const bool vec = g16_vec_ok(n, reinterpret_cast<uintptr_t>(b), reinterpret_cast<uintptr_t>(mul));
   if (vec) {   // 16 threads x 16 bytes per row, 16 rows per pass: the four passes' loads go out together
     const int cc = (tid & 15) * 4, rr = tid >> 4;
     f32x4 v[4];
@@ -1109,13 +1128,48 @@ static void g16_launch(const Gemm16Args &g, bool big, hipStream_t s) {
   }
 }
 
+// What gemm16_run_ex launches for one product: the kernel choice decides the image layout, the split its K slices.
+// gemm16_run_ex and tfrs_gemm_plan both ask this function.
+struct G16Plan {
+  G16Layout L;
+  bool splitk, big;
+  int kb;              // K block of the images: 16 (K-step-major, 256 x 256 kernel) or kp (plain rows)
+  unsigned nslab;      // 256-row slabs of the column-maximum pass
+  int kt_per, slices;  // split-K: K steps of 16 per slice (0 = no split), number of non-empty slices
+};
+static G16Plan g16_plan(int64_t m, int n, int k, int epi, bool has_bias, bool act_or_pre) {
+  G16Plan P;
+  P.L = g16_layout(m, n, k);
+  const G16Layout &L = P.L;
+  P.nslab = (unsigned)((k + kG16Slab - 1) / kG16Slab);
+  // kernel choice first: it decides the image layout
+  const char *tv = option("TFRS_GEMM16_TILE");
+  const int forced = (tv && *tv) ? atoi(tv) : 0;
+  const int64_t big_tiles = (L.mp / kB16M) * (L.np / kB16N);
+  P.splitk = L.nsplit > 1 && epi == kG16EpiBias && !has_bias && !act_or_pre && forced != 128;
+  P.big = (forced == 256 || (forced != 128 && big_tiles >= 512) || P.splitk) && n < (1 << 23);   // (32-bit tile offsets in its epilogue)
+  // the 256 x 256 kernel reads K-step-major images (kb = 16 halves): the operand tile of one K
+  // step is 256 rows x 32 bytes CONTIGUOUS, so every direct-to-LDS copy instruction moves eight
+  // full 128-byte lines instead of 32 quarter lines 2 * kp bytes apart
+  P.kb = P.big ? kB16K : L.kp;
+  P.kt_per = 0;
+  P.slices = 1;
+  if (P.splitk) {
+    const int nk_all = L.kp / kB16K;
+    P.kt_per = (nk_all + L.nsplit - 1) / L.nsplit;
+    P.slices = (nk_all + P.kt_per - 1) / P.kt_per;
+  }
+  return P;
+}
+
 // C = A @ B (+ bias) with epilogue `epi` on (e0, e1, diag); colsum (optional, B not transposed):
 // colsum[n] = sum_k (B * mul)[k, n].  ws from gemm16_workspace_bytes(m, n, k).
 int gemm16_run_ex(const G16Operand &a, const G16Operand &b, int64_t m, int n, int k,
                   const float *bias, int epi, const float *e0, const float *e1, float diag,
                   float *out, float *colsum, void *ws, hipStream_t s, float *aux = nullptr, int act = 0,
                   float *pre = nullptr) {
-  const G16Layout L = g16_layout(m, n, k);
+  const G16Plan P = g16_plan(m, n, k, epi, bias != nullptr, act || pre);
+  const G16Layout &L = P.L;
   char *w = static_cast<char *>(ws);
   _Float16 *ah = reinterpret_cast<_Float16 *>(w + L.ah), *al = reinterpret_cast<_Float16 *>(w + L.al);
   _Float16 *bh = reinterpret_cast<_Float16 *>(w + L.bh), *bl = reinterpret_cast<_Float16 *>(w + L.bl);
@@ -1123,17 +1177,9 @@ int gemm16_run_ex(const G16Operand &a, const G16Operand &b, int64_t m, int n, in
   uint32_t *colmax = reinterpret_cast<uint32_t *>(w + L.colmax);
   uint32_t *colmax_a = reinterpret_cast<uint32_t *>(w + L.colmax_a);
   float *psum = reinterpret_cast<float *>(w + L.psum);
-  const unsigned nslab = (unsigned)((k + kG16Slab - 1) / kG16Slab);
-  // kernel choice first: it decides the image layout
-  const char *tv = option("TFRS_GEMM16_TILE");
-  const int forced = (tv && *tv) ? atoi(tv) : 0;
-  const int64_t big_tiles = (L.mp / kB16M) * (L.np / kB16N);
-  const bool splitk = L.nsplit > 1 && epi == kG16EpiBias && !bias && !act && !pre && forced != 128;
-  const bool big = (forced == 256 || (forced != 128 && big_tiles >= 512) || splitk) && n < (1 << 23);   // (32-bit tile offsets in its epilogue)
-  // the 256 x 256 kernel reads K-step-major images (kb = 16 halves): the operand tile of one K
-  // step is 256 rows x 32 bytes CONTIGUOUS, so every direct-to-LDS copy instruction moves eight
-  // full 128-byte lines instead of 32 quarter lines 2 * kp bytes apart
-  const int kb = big ? kB16K : L.kp;
+  const unsigned nslab = P.nslab;
+  const bool splitk = P.splitk, big = P.big;
+  const int kb = P.kb;
   // column maxima are combined with atomicMax: re-armed by a kernel, not a memset node
   hipLaunchKernelGGL(g16_zero_kernel, dim3((unsigned)((L.np + L.mp + 255) / 256)), dim3(256), 0, s,
                      colmax, (int)(L.np + L.mp));   // colmax and colmax_a are adjacent
@@ -1185,9 +1231,8 @@ int gemm16_run_ex(const G16Operand &a, const G16Operand &b, int64_t m, int n, in
   // large shapes: 256 x 256 tiles with the 4-deep ring; otherwise (few tiles: fill the chip)
   // the 128 x 128 kernel.  TFRS_GEMM16_TILE = 128 | 256 forces one.
   if (splitk) {
-    const int nk_all = L.kp / kB16K;
-    g.kt_per = (nk_all + L.nsplit - 1) / L.nsplit;
-    const int slices = (nk_all + g.kt_per - 1) / g.kt_per;
+    g.kt_per = P.kt_per;
+    const int slices = P.slices;
     g.out = reinterpret_cast<float *>(w + L.part);
     const dim3 grid((unsigned)(((m + kB16M - 1) / kB16M) * ((n + kB16N - 1) / kB16N)), (unsigned)slices);
     hipLaunchKernelGGL((gemm16_big_kernel<kG16EpiBias>), grid, dim3(512), 0, s, g);
@@ -1342,6 +1387,31 @@ int gemm16_dense_bwd(const float *x, const float *kernel, const float *dy, int64
                        (int)nslab, dout, dbias);
     TFRS_LAUNCH_CHECK();
   }
+  return TFRS_OK;
+}
+
+// The f16 half of tfrs_gemm_plan (interaction.hip): host only.  flags / align as declared in tfrs_hip.h.
+int gemm16_plan(int64_t m, int n, int k, int flags, int align, int64_t *out) {
+  const bool at = flags & 1, bt = flags & 2, amul = flags & 4, bmul = flags & 8;
+  const uintptr_t la = align & 15, lb = (align >> 4) & 15;
+  const uintptr_t lam = amul ? (align >> 8) & 15 : 0, lbm = bmul ? (align >> 12) & 15 : 0;
+  const G16Plan P = g16_plan(m, n, k, (flags & 16) ? kG16EpiCross : kG16EpiBias, (flags & 32) != 0, (flags & 64) != 0);
+  const int nk_all = P.L.kp / kB16K;
+  out[0] = P.big; out[1] = P.L.kp; out[2] = P.L.mp; out[3] = P.L.np; out[4] = P.kb; out[5] = P.nslab;
+  out[6] = P.L.nsplit; out[7] = P.kt_per; out[8] = P.slices;
+  out[9] = P.splitk ? nk_all - (P.slices - 1) * P.kt_per : nk_all;
+  // per operand: kind (0 row-per-wave kernel, 1 column pass, 2 single-pass K-step-major, 3 its two-pass fallback),
+  // steps, v2, waves, 16-byte loads
+  auto operand = [&](bool cols, int64_t ld, uintptr_t lp, uintptr_t lm, int64_t *o) {
+    o[0] = cols ? 1 : 0; o[1] = 0; o[2] = 0; o[3] = 0;
+    if (!cols && P.kb == kB16K) {
+      const G16RowPrep v = g16_row_prep(k, P.L.kp, lp, lm);
+      o[0] = v.steps ? 2 : 3; o[1] = v.steps; o[2] = v.v2; o[3] = v.waves;
+    }
+    o[4] = g16_vec_ok(ld, lp, lm);
+  };
+  operand(at, at ? m : (int64_t)k, la, lam, out + 10);
+  operand(!bt, bt ? (int64_t)k : (int64_t)n, lb, lbm, out + 15);
   return TFRS_OK;
 }
 

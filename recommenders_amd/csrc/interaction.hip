@@ -63,6 +63,12 @@ struct GemmArgs {
   float *pre;
 };
 
+// 16-byte loads of an operand with rows of `ld` floats (and of its multiplier, 0 = none).  One predicate for the
+// kernel and for tfrs_gemm_plan (which passes the low address bits only).
+__host__ __device__ __forceinline__ bool gemm_vec_ok(int64_t ld, uintptr_t p, uintptr_t mul) {
+  return (ld % 4 == 0) && (p % 16 == 0) && (mul % 16 == 0);
+}
+
 // AT: `a` holds A^T ([K, M] row-major); BT: `b` holds B^T ([N, K] row-major).  The tiles are
 // transposed on their way into LDS, so dW = x^T dz and dx = dz W^T read x, dz and W as they lie.
 template <int EPI, bool AT, bool BT>
@@ -81,10 +87,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs g) {
   const int64_t bm = (int64_t)(blockIdx.x / nbn) * kBM;
   const int bn = (int)(blockIdx.x % nbn) * kBN;
 
-  const bool a_vec = ((AT ? g.m : (int64_t)g.k) % 4 == 0) && (((uintptr_t)g.a) % 16 == 0) &&
-                     (!g.amul || ((uintptr_t)g.amul) % 16 == 0);
-  const bool b_vec = ((BT ? g.k : g.n) % 4 == 0) && (((uintptr_t)g.b) % 16 == 0) &&
-                     (!g.bmul || ((uintptr_t)g.bmul) % 16 == 0);
+  const bool a_vec = gemm_vec_ok(AT ? g.m : (int64_t)g.k, (uintptr_t)g.a, (uintptr_t)g.amul);
+  const bool b_vec = gemm_vec_ok(BT ? g.k : g.n, (uintptr_t)g.b, (uintptr_t)g.bmul);
   // 4 consecutive elements of a row-major [rows, ld] array (zero outside), optional multiplier
   auto load4 = [&](const float *p, const float *mul, int64_t r, int64_t c, int64_t rows, int64_t ld,
                    bool vec) -> f32x4 {
@@ -1916,6 +1920,19 @@ static int splitk_slices(int64_t m, int n, int64_t k) {
   want = std::min<int64_t>(want, std::max<int64_t>(1, (int64_t)(16 << 20) / std::max<int64_t>(1, m * n)));
   return (int)std::max<int64_t>(1, want);
 }
+// The slices launch_gemm cuts K into: `kper` rows each (whole kBK steps), `used` of them non-empty.  launch_gemm and
+// tfrs_gemm_plan both ask this function.
+struct SplitK {
+  int slices, kper, used;
+};
+static SplitK splitk_geometry(int64_t m, int n, int64_t k) {
+  SplitK g = {splitk_slices(m, n, k), 0, 1};
+  if (g.slices > 1) {
+    g.kper = (int)((k + g.slices - 1) / g.slices + kBK - 1) / kBK * kBK;
+    g.used = (int)((k + g.kper - 1) / g.kper);
+  }
+  return g;
+}
 static size_t splitk_bytes(int64_t m, int n, int64_t k) {
   const int sl = splitk_slices(m, n, k);
   return sl > 1 ? (size_t)sl * (size_t)m * (size_t)n * sizeof(float) : 0;
@@ -1942,10 +1959,10 @@ static int launch_gemm(const GemmArgs &g_in, int epi, hipStream_t s, bool at = f
   const int nbn = (g.n + kBN - 1) / kBN;
   const dim3 grid((unsigned)(nbm * nbn));
   if (at) {          // dW = x^T dz
-    const int slices = splitk_ws ? splitk_slices(g.m, g.n, g.k) : 1;
-    if (slices > 1) {
-      g.kper = (int)(((int64_t)g.k + slices - 1) / slices + kBK - 1) / kBK * kBK;
-      const int used = (int)(((int64_t)g.k + g.kper - 1) / g.kper);
+    const SplitK sk = splitk_ws ? splitk_geometry(g.m, g.n, g.k) : SplitK{1, 0, 1};
+    if (sk.slices > 1) {
+      g.kper = sk.kper;
+      const int used = sk.used;
       float *const final_out = g.out;
       g.out = splitk_ws;
       hipLaunchKernelGGL((gemm_kernel<kEpiBias, true, false>), dim3(grid.x, (unsigned)used), dim3(256), 0, s, g);
@@ -2322,6 +2339,33 @@ extern "C" int tfrs_cross_bwd_f16(const float *x0, const float *x, const float *
   }
   return gemm16_cross_bwd(x0, x, kernel, bias, diag_scale, dy, batch, d, dx0, dx, dkernel, dbias,
                           workspace, (hipStream_t)stream);
+}
+
+// ---- what the GEMM launchers would choose at a shape (host only; see tfrs_hip.h) ---------------
+namespace tfrs {
+int gemm16_plan(int64_t m, int n, int k, int flags, int align, int64_t *out);
+}
+extern "C" int tfrs_gemm_plan(int f16, int64_t m, int n, int64_t k, int flags, int align, int64_t *out) {
+  TFRS_CHECK_ARG(out != nullptr, "gemm_plan: NULL pointer");
+  TFRS_CHECK_ARG(f16 == 0 || f16 == 1, "gemm_plan: f16 must be 0 or 1");
+  TFRS_CHECK_ARG(m >= 1 && n >= 1 && k >= 1 && m <= 0x7FFFFFFFll && k <= 0x7FFFFFFFll, "gemm_plan: bad shape");
+  TFRS_CHECK_ARG(flags >= 0 && flags < 128, "gemm_plan: unknown flag in %d", flags);
+  TFRS_CHECK_ARG(align >= 0 && align <= 0xFFFF && (align & 0x3333) == 0,
+                 "gemm_plan: `align` holds the low four address bits of four float pointers");
+  const bool at = flags & 1, bt = flags & 2;
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  if (f16) return gemm16_plan(m, n, (int)k, flags, align, out);
+  TFRS_CHECK_ARG(!(at && bt), "gemm_plan: the f32 kernel has no A^T B^T product");
+  // (the split exists for the A^T B products only: launch_gemm gets its scratch from both backward entries)
+  const SplitK sk = at ? splitk_geometry(m, n, k) : SplitK{1, 0, 1};
+  out[0] = sk.slices; out[1] = sk.kper; out[2] = sk.used;
+  out[3] = sk.slices > 1 ? k - (int64_t)(sk.used - 1) * sk.kper : k;
+  const uintptr_t la = align & 15, lb = (align >> 4) & 15;
+  const uintptr_t lam = (flags & 4) ? (align >> 8) & 15 : 0, lbm = (flags & 8) ? (align >> 12) & 15 : 0;
+  out[4] = gemm_vec_ok(at ? m : k, la, lam);
+  out[5] = gemm_vec_ok(bt ? k : (int64_t)n, lb, lbm);
+  out[6] = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
+  return TFRS_OK;
 }
 
 extern "C" size_t tfrs_gemm_f16_workspace_bytes(int64_t m, int n, int k) {
