@@ -687,6 +687,19 @@ int tfrs_listwise_loss_bwd(int kind, const float *labels, const float *scores, i
                            const float *scale, float *dscores, void *stream);
 int tfrs_listwise_ndcg(const float *labels, const float *scores, int64_t nlists, int len, int topn, float *ndcg,
                        float *counted, void *stream);
+/* The two pairwise kinds with LambdaRank / LambdaLoss pair weights (losses.DCGLambdaWeight / NDCGLambdaWeight; formulas:
+ * DESIGN 4.25): every pair term is multiplied by
+ *   w_ij = |G_i - G_j| * ((1 - smooth_fraction) * |D(r_i) - D(r_j)| + smooth_fraction * |D0(d) - D0(d + 1)|),
+ * r = the rank by score (descending, ties by position ascending), d = |r_i - r_j|, D0(r) = 1 / log2(r + 1), D = D0 cut to
+ * 0 beyond rank topn (topn == 0: no cut; w_ij = 0 when both ranks lie beyond it), G = 2^label - 1, divided by the
+ * list's IDCG@topn when `normalized` (every weight 0 where that is not positive).  The weights are constants of the
+ * backward.  Same envelope, same validity rule, one launch each on `stream`, no workspace, no atomics.  TFRS_EINVAL
+ * before any device call for a kind other than the two pairwise ones, topn < 0 or a smooth_fraction outside [0, 1]
+ * (NaN included). */
+int tfrs_listwise_lambda_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len, int topn,
+                             int normalized, float smooth_fraction, float *loss, void *stream);
+int tfrs_listwise_lambda_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len, int topn,
+                             int normalized, float smooth_fraction, const float *scale, float *dscores, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Cross.call (layers/feature_interaction/dcn.py:151-186), full rank, linear

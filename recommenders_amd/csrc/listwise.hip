@@ -1,5 +1,6 @@
 // listwise.hip -- listwise ranking losses (softmax, pairwise logistic, pairwise hinge, ListMLE) with their gradients,
-// and per-list NDCG, on [nlists, len] label / score matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24).
+// the two pairwise ones also with LambdaRank / LambdaLoss pair weights, and per-list NDCG, on [nlists, len] label /
+// score matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24, 4.25).
 //
 // Position i of a list is VALID iff label[i] >= 0 (-1 pads; a NaN label is not valid either).  Invalid positions are
 // selected out when the list is loaded -- their score is replaced by 0 and never enters any arithmetic -- and their
@@ -30,6 +31,14 @@
 //   softmax        max, sum of exp(s - max), sum of y (lse - s), sum of y: group sums.
 //   NDCG           two sorts (by score: DCG, by label: IDCG); each a group sum over the ranks r < min(n, topn) of
 //                  (2^y - 1) / log2(r + 2).
+//   lambda weights the pairwise walk above with every term multiplied by w_ij before it is added; separate
+//                  kernels (listwise_lambda_kernel), the unweighted ones carry no trace of them.  A sort by score; the
+//                  thread at sorted slot r scatters rank r + 1 and the discount D(r + 1) to its item's position.  When
+//                  normalised, first a sort by label and IDCG as in NDCG: a group sum over the ranks
+//                  r < min(n, topn).  Per position, once: gain (2^y - 1), divided by IDCG when normalised (0 when
+//                  IDCG <= 0).  Gains, discounts, ranks and (smooth) the table u(delta) = |D0(delta) - D0(delta + 1)|
+//                  live in the four scan buffers.  w_ij = |G_i - G_j| * |D_i - D_j|, or, smooth,
+//                  |G_i - G_j| * ((1 - mu) * |D_i - D_j| + mu * u(|r_i - r_j|)), evaluated in that order.
 #include "common.h"
 
 namespace tfrs {
@@ -375,6 +384,145 @@ __global__ void __launch_bounds__(kLwThreads) listwise_ndcg_kernel(const float *
   }
 }
 
+// ---- lambda weights (LambdaRank / LambdaLoss pair weights on the DCG or NDCG gain) -----------------------
+// The per-position quantities of the weights in the scan buffers, which the pairwise kinds leave free.
+template <int G>
+struct LwLambda {
+  float *gain, *disc, *rank, *table;
+  __device__ __forceinline__ LwLambda(LwShared<G> &sh, int off)
+      : gain(sh.m[0] + off), disc(sh.m[1] + off), rank(sh.a[0] + off), table(sh.a[1] + off) {}
+};
+
+__device__ __forceinline__ float lw_discount(int r) { return 1.0f / log2f((float)(r + 1)); }   // D0(r), r = 1, 2, ...
+
+// Fills the buffers of LwLambda for the loaded list: entry barrier done (lw_load), ends with a barrier.
+template <int G, bool SMOOTH>
+__device__ __forceinline__ void lw_lambda_prepare(const LwList<G> &l, LwShared<G> &sh, int P, int topn,
+                                                  int normalized) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  LwLambda<G> lam(sh, l.off);
+  const int lim = topn > 0 && topn < P ? topn : P;
+  float idcg = 1.0f;
+  if (normalized) {                                   // (a kernel argument: uniform)
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      sh.key[l.off + i] = l.valid[c] ? make_key(l.yv[c], i) : 0ull;
+    }
+    __syncthreads();
+    lw_sort<G>(l, sh, P);
+    float t = 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int r = l.sub + G * c;
+      const uint64_t k = r < lim ? sh.key[l.off + r] : 0ull;
+      if (k != 0ull) t += (exp2f(sh.y[l.off + key_index(k)]) - 1.0f) / log2f((float)(r + 2));
+    }
+    idcg = lw_sum<G>(t, sh.red);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) {
+    const int i = l.sub + G * c;
+    sh.key[l.off + i] = l.valid[c] ? make_key(l.sv[c], i) : 0ull;
+    float g = l.valid[c] ? exp2f(l.yv[c]) - 1.0f : 0.0f;
+    if (normalized) g = idcg > 0.0f ? g / idcg : 0.0f;
+    lam.gain[i] = g;
+    lam.disc[i] = 0.0f;                               // (invalid positions: never read by a pair, but defined)
+    lam.rank[i] = 0.0f;
+    if (SMOOTH) lam.table[i] = i >= 1 ? fabsf(lw_discount(i) - lw_discount(i + 1)) : 0.0f;
+  }
+  __syncthreads();
+  lw_sort<G>(l, sh, P);
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) {
+    const int r = l.sub + G * c;
+    const uint64_t k = r < P ? sh.key[l.off + r] : 0ull;
+    if (k != 0ull) {                                  // one sorted slot per valid position: disjoint writes
+      const int pos = key_index(k);
+      lam.disc[pos] = r < lim ? lw_discount(r + 1) : 0.0f;
+      lam.rank[pos] = (float)(r + 1);
+    }
+  }
+  __syncthreads();
+}
+
+// lw_pairs with every term multiplied by its pair weight.
+template <int G, bool HINGE, bool BWD, bool SMOOTH>
+__device__ __forceinline__ void lw_lambda_pairs(const LwList<G> &l, LwShared<G> &sh, int len, int topn, float mu,
+                                                float *acc) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  const LwLambda<G> lam(sh, l.off);
+  const float cut = topn > 0 ? (float)topn : __builtin_inff();
+  const float nu = 1.0f - mu;
+  float gi[IPT], di[IPT], ri[IPT];
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) {
+    const int i = l.sub + G * c;
+    acc[c] = 0.0f;
+    gi[c] = lam.gain[i];
+    di[c] = lam.disc[i];
+    ri[c] = lam.rank[i];
+  }
+  for (int j = 0; j < len; ++j) {
+    const float yj = sh.y[l.off + j], sj = sh.s[l.off + j];
+    if (!(yj >= 0.0f)) continue;
+    const float gj = lam.gain[j], dj = lam.disc[j];
+    const float rj = SMOOTH ? lam.rank[j] : 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      if (!l.valid[c]) continue;
+      const float yi = l.yv[c], si = l.sv[c];
+      if (!(yi > yj) && !(BWD && yj > yi)) continue;
+      float w = fabsf(di[c] - dj);
+      if (SMOOTH) {
+        const float u = lam.table[(int)fabsf(ri[c] - rj)];          // 1 <= |r_i - r_j| <= n - 1 < CAP
+        w = fminf(ri[c], rj) > cut ? 0.0f : nu * w + mu * u;
+      }
+      w = fabsf(gi[c] - gj) * w;
+      if (yi > yj) {
+        const float x = si - sj;
+        if (BWD) acc[c] += w * (HINGE ? (x < 1.0f ? -1.0f : 0.0f) : lw_logistic_grad(x));
+        else acc[c] += w * (HINGE ? fmaxf(0.0f, 1.0f - x) : lw_logistic(x));
+      } else {
+        const float x = sj - si;
+        acc[c] -= w * (HINGE ? (x < 1.0f ? -1.0f : 0.0f) : lw_logistic_grad(x));
+      }
+    }
+  }
+}
+
+template <int G, bool BWD, bool SMOOTH>
+__global__ void __launch_bounds__(kLwThreads) listwise_lambda_kernel(int kind, const float *__restrict__ labels,
+                                                                     const float *__restrict__ scores, int64_t nlists,
+                                                                     int len, int P, int topn, int normalized, float mu,
+                                                                     const float *__restrict__ scale,
+                                                                     float *__restrict__ out) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  __shared__ LwShared<G> sh;
+  LwList<G> l;
+  lw_load<G>(l, sh, labels, scores, nlists, len);
+  const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
+  const float sc = (BWD && l.active) ? scale[list] : 0.0f;
+  lw_lambda_prepare<G, SMOOTH>(l, sh, P, topn, normalized);
+  float acc[IPT];
+  if (kind == kLwPairHinge) lw_lambda_pairs<G, true, BWD, SMOOTH>(l, sh, len, topn, mu, acc);
+  else lw_lambda_pairs<G, false, BWD, SMOOTH>(l, sh, len, topn, mu, acc);
+  if (BWD) {
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      if (l.active && i < len) out[l.base + i] = l.valid[c] ? sc * acc[c] : 0.0f;
+    }
+  } else {
+    float t = 0.0f;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) t += acc[c];
+    const float loss = lw_sum<G>(t, sh.red);
+    if (l.active && l.sub == 0) out[list] = loss;
+  }
+}
+
 static int lw_group(int len) { return len <= 8 ? 8 : len <= 16 ? 16 : len <= 32 ? 32 : len <= 64 ? 64 : 256; }
 static int lw_pow2(int len, int g) {
   int p = g < 256 ? g : 128;
@@ -406,6 +554,19 @@ static int lw_check_shape(const char *what, int64_t nlists, int len) {
 #define TFRS_LW_FWD(G) listwise_loss_kernel<G, false>
 #define TFRS_LW_BWD(G) listwise_loss_kernel<G, true>
 #define TFRS_LW_NDCG(G) listwise_ndcg_kernel<G>
+#define TFRS_LW_LAMBDA_FWD(G) listwise_lambda_kernel<G, false, false>
+#define TFRS_LW_LAMBDA_FWD_SMOOTH(G) listwise_lambda_kernel<G, false, true>
+#define TFRS_LW_LAMBDA_BWD(G) listwise_lambda_kernel<G, true, false>
+#define TFRS_LW_LAMBDA_BWD_SMOOTH(G) listwise_lambda_kernel<G, true, true>
+
+static int lw_check_lambda(const char *what, int kind, int topn, float smooth_fraction) {
+  TFRS_CHECK_ARG(kind == kLwPairLogistic || kind == kLwPairHinge,
+                 "%s: kind %d takes no lambda weight (pairwise logistic and pairwise hinge do)", what, kind);
+  TFRS_CHECK_ARG(topn >= 0, "%s: topn=%d must be positive, or 0 for no cut", what, topn);
+  TFRS_CHECK_ARG(smooth_fraction >= 0.0f && smooth_fraction <= 1.0f, "%s: smooth_fraction=%g outside [0, 1]", what,
+                 (double)smooth_fraction);
+  return TFRS_OK;
+}
 
 }  // namespace tfrs
 
@@ -444,6 +605,42 @@ extern "C" int tfrs_listwise_ndcg(const float *labels, const float *scores, int6
   TFRS_CHECK_ARG(labels && scores && ndcg && counted, "listwise_ndcg: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   TFRS_LW_DISPATCH(TFRS_LW_NDCG, labels, scores, nlists, len, P, topn, ndcg, counted);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_lambda_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                        int topn, int normalized, float smooth_fraction, float *loss, void *stream) {
+  if (int rc = lw_check_lambda("listwise_lambda_fwd", kind, topn, smooth_fraction)) return rc;
+  if (int rc = lw_check_shape("listwise_lambda_fwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && loss, "listwise_lambda_fwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const float *no_scale = nullptr;
+  if (smooth_fraction != 0.0f)
+    TFRS_LW_DISPATCH(TFRS_LW_LAMBDA_FWD_SMOOTH, kind, labels, scores, nlists, len, P, topn, normalized, smooth_fraction,
+                     no_scale, loss);
+  else
+    TFRS_LW_DISPATCH(TFRS_LW_LAMBDA_FWD, kind, labels, scores, nlists, len, P, topn, normalized, smooth_fraction,
+                     no_scale, loss);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_lambda_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                        int topn, int normalized, float smooth_fraction, const float *scale,
+                                        float *dscores, void *stream) {
+  if (int rc = lw_check_lambda("listwise_lambda_bwd", kind, topn, smooth_fraction)) return rc;
+  if (int rc = lw_check_shape("listwise_lambda_bwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && scale && dscores, "listwise_lambda_bwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (smooth_fraction != 0.0f)
+    TFRS_LW_DISPATCH(TFRS_LW_LAMBDA_BWD_SMOOTH, kind, labels, scores, nlists, len, P, topn, normalized, smooth_fraction,
+                     scale, dscores);
+  else
+    TFRS_LW_DISPATCH(TFRS_LW_LAMBDA_BWD, kind, labels, scores, nlists, len, P, topn, normalized, smooth_fraction, scale,
+                     dscores);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }

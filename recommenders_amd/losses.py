@@ -70,7 +70,8 @@ class MeanSquaredError(_Loss):
 # Listwise ranking losses: y_true / y_pred are [batch, list]; a position is valid iff
 # y_true >= 0 (-1 pads, TF-Ranking's convention).  One fused HIP kernel per direction
 # (csrc/listwise.hip): a list lives in LDS and registers, no [B, L, L] tensor exists, the backward
-# recomputes from the two inputs.  sample_weight is PER LIST ([B] or [B, 1]).
+# recomputes from the two inputs.  sample_weight is PER LIST ([B] or [B, 1]).  The two pairwise losses take
+# lambda_weight= (DCGLambdaWeight / NDCGLambdaWeight): separate kernels of the same file.
 # ------------------------------------------------------------------------------------------------
 MAX_LIST_LEN = 1024
 _SOFTMAX, _PAIRWISE_LOGISTIC, _PAIRWISE_HINGE, _LIST_MLE = 0, 1, 2, 3
@@ -124,11 +125,90 @@ class _ListwiseFn(torch.autograd.Function):
     return ds, None, None
 
 
+class DCGLambdaWeight:
+  """LambdaRank / LambdaLoss pair weights on the DCG gain, for ``PairwiseLogisticLoss`` / ``PairwiseHingeLoss``
+  (``lambda_weight=``).  With ``r`` the rank of a valid item by score (descending, ties by position
+  ascending), ``D0(r) = 1 / log2(r + 1)``, ``D(r) = D0(r)`` up to rank ``topn`` and 0 beyond it, ``G = 2^y - 1`` (divided
+  by the list's ideal DCG@topn when ``normalized``; every weight of a list whose ideal DCG is not positive is 0) and
+  ``d = |r_i - r_j|``, the term of the pair ``(i, j)`` is multiplied by
+
+      ``w_ij = |G_i - G_j| ((1 - smooth_fraction) |D(r_i) - D(r_j)| + smooth_fraction |D0(d) - D0(d + 1)|)``
+
+  and by 0 when both ranks lie beyond ``topn``.  ``smooth_fraction = 0`` is LambdaRank (``w_ij`` = the change of the
+  metric when the two items swap ranks), a positive one LambdaLoss.  The weights are constants of the backward pass.
+  Labels must keep ``2^y`` finite in float32 (``y < 128``), as for ``NDCGMetric``."""
+
+  def __init__(self, topn: Optional[int] = None, normalized: bool = False, smooth_fraction: float = 0.0):
+    name = type(self).__name__
+    try:
+      ok = topn is None or (not isinstance(topn, bool) and int(topn) == topn and topn >= 1)
+    except (TypeError, ValueError, OverflowError):
+      ok = False
+    if not ok:
+      raise ValueError(f"{name}: topn must be a positive integer or None, got {topn!r}")
+    try:
+      ok = not isinstance(smooth_fraction, bool) and 0.0 <= float(smooth_fraction) <= 1.0      # (NaN fails both)
+    except (TypeError, ValueError):
+      ok = False
+    if not ok:
+      raise ValueError(f"{name}: smooth_fraction must lie in [0, 1], got {smooth_fraction!r}")
+    self.topn = None if topn is None else int(topn)
+    self.normalized = bool(normalized)
+    self.smooth_fraction = float(smooth_fraction)
+
+
+class NDCGLambdaWeight(DCGLambdaWeight):
+  """``DCGLambdaWeight`` normalised by the list's ideal DCG: the pair weights of the NDCG metric."""
+
+  def __init__(self, topn: Optional[int] = None, smooth_fraction: float = 0.0):
+    super().__init__(topn=topn, normalized=True, smooth_fraction=smooth_fraction)
+
+
+class _ListwiseLambdaFn(torch.autograd.Function):
+  """``_ListwiseFn`` for a pairwise kind with lambda weights, over ``tfrs_listwise_lambda_fwd`` / ``_bwd``: the backward
+  recomputes ranks and weights from the two inputs, nothing else is kept."""
+
+  @staticmethod
+  def forward(ctx, y_pred, y_true, kind, topn, normalized, smooth_fraction):
+    from recommenders_amd import _lib
+    b, l = y_pred.shape
+    loss = torch.empty((b,), dtype=torch.float32, device=y_pred.device)
+    _lib.check(_lib.load().tfrs_listwise_lambda_fwd(kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l, topn, normalized,
+                                                     smooth_fraction, _lib.ptr(loss), _lib.current_stream()))
+    ctx.save_for_backward(y_true, y_pred)
+    ctx.args = (kind, topn, normalized, smooth_fraction)
+    return loss
+
+  @staticmethod
+  def backward(ctx, grad):
+    from recommenders_amd import _lib
+    y_true, y_pred = ctx.saved_tensors
+    kind, topn, normalized, smooth_fraction = ctx.args
+    b, l = y_pred.shape
+    scale = grad.to(torch.float32).contiguous()
+    ds = torch.empty_like(y_pred)
+    _lib.check(_lib.load().tfrs_listwise_lambda_bwd(kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l, topn, normalized,
+                                                     smooth_fraction, _lib.ptr(scale), _lib.ptr(ds),
+                                                     _lib.current_stream()))
+    return ds, None, None, None, None, None
+
+
 class _ListwiseLoss(_Loss):
   _KIND = None
+  lambda_weight = None
+
+  def _set_lambda_weight(self, lambda_weight):
+    if lambda_weight is not None and not isinstance(lambda_weight, DCGLambdaWeight):
+      raise ValueError(f"{type(self).__name__}: lambda_weight must be a DCGLambdaWeight, an NDCGLambdaWeight or None, "
+                       f"got {lambda_weight!r}")
+    self.lambda_weight = lambda_weight
 
   def _per_sample(self, y_true, y_pred):
-    return _ListwiseFn.apply(y_pred, y_true, self._KIND)
+    lw = self.lambda_weight
+    if lw is None:
+      return _ListwiseFn.apply(y_pred, y_true, self._KIND)
+    topn = 0 if lw.topn is None else min(lw.topn, 2 ** 31 - 1)
+    return _ListwiseLambdaFn.apply(y_pred, y_true, self._KIND, topn, int(lw.normalized), lw.smooth_fraction)
 
   def __call__(self, y_true, y_pred, sample_weight=None) -> torch.Tensor:
     y_true, y_pred = _listwise_inputs(y_true, y_pred, type(self).__name__, sample_weight)
@@ -148,19 +228,25 @@ class SoftmaxLoss(_ListwiseLoss):
 
 
 class PairwiseLogisticLoss(_ListwiseLoss):
-  """``sum_{y_i > y_j} log(1 + exp(-(s_i - s_j)))`` over the valid pairs of a list."""
+  """``sum_{y_i > y_j} w_ij log(1 + exp(-(s_i - s_j)))`` over the valid pairs of a list; ``w_ij = 1``, or the pair
+  weights of ``lambda_weight`` (a ``DCGLambdaWeight`` / ``NDCGLambdaWeight``: LambdaRank, LambdaLoss)."""
   _KIND = _PAIRWISE_LOGISTIC
 
-  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_logistic_loss"):
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_logistic_loss",
+               lambda_weight: Optional[DCGLambdaWeight] = None):
     super().__init__(reduction, name)
+    self._set_lambda_weight(lambda_weight)
 
 
 class PairwiseHingeLoss(_ListwiseLoss):
-  """``sum_{y_i > y_j} max(0, 1 - (s_i - s_j))`` over the valid pairs of a list."""
+  """``sum_{y_i > y_j} w_ij max(0, 1 - (s_i - s_j))`` over the valid pairs of a list; ``w_ij`` as for
+  ``PairwiseLogisticLoss``."""
   _KIND = _PAIRWISE_HINGE
 
-  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_hinge_loss"):
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "pairwise_hinge_loss",
+               lambda_weight: Optional[DCGLambdaWeight] = None):
     super().__init__(reduction, name)
+    self._set_lambda_weight(lambda_weight)
 
 
 class ListMLELoss(_ListwiseLoss):
