@@ -687,6 +687,35 @@ int tfrs_listwise_loss_bwd(int kind, const float *labels, const float *scores, i
                            const float *scale, float *dscores, void *stream);
 int tfrs_listwise_ndcg(const float *labels, const float *scores, int64_t nlists, int len, int topn, float *ndcg,
                        float *counted, void *stream);
+/* The list metrics of one step out of ONE launch (metrics/listwise.py; formulas: DESIGN 4.26): the list is loaded once
+ * and sorted by score once for every requested metric.  kinds[m] / topns[m], m < nmetrics <= TFRS_LISTWISE_METRIC_MAX,
+ * are HOST arrays, read before the launch (they travel as a kernel argument: no copy, the call can be captured);
+ * topns[m] == 0 means no cut.  values[m * nlists + l] is metric m's value of list l and weights[m * nlists + l] its
+ * non-negative weight (value +0 where the weight is 0); a metric's result over lists is sum w v / sum w.  With
+ * rel = [label >= 1], R the relevant items of the list, c_r those at score ranks <= r and k = min(n, topn):
+ *   NDCG       DCG / IDCG as tfrs_listwise_ndcg (bit for bit), weight [IDCG > 0]
+ *   DCG        sum_{r<k} (2^y - 1) / log2(r + 2), weight [some label > 0]
+ *   MRR        1 / (first relevant rank below k, 1-based), 0 if none        weight [R > 0] for these five
+ *   HITS       1 if a relevant item ranks below k, else 0
+ *   PRECISION  c_{k-1} / min(topn, len)   (len, the padded width, when topn == 0)
+ *   RECALL     c_{k-1} / R
+ *   MAP        (sum over the relevant ranks r < k of c_r / (r + 1)) / R
+ *   ARP        sum_V y (r + 1) / sum_V y, weight sum_V y                     (no topn)
+ *   OPA        C / P, P = pairs with y_i > y_j, C = those with s_i > s_j (a tie is wrong), weight P   (no topn)
+ * TFRS_EINVAL before any device call: nmetrics outside 1 .. TFRS_LISTWISE_METRIC_MAX, an unknown kind, topn < 0, a
+ * non-zero topn for ARP or OPA, a NULL pointer, a shape outside the envelope above. */
+#define TFRS_LISTWISE_METRIC_MAX 16
+#define TFRS_LISTWISE_METRIC_NDCG 0
+#define TFRS_LISTWISE_METRIC_DCG 1
+#define TFRS_LISTWISE_METRIC_MRR 2
+#define TFRS_LISTWISE_METRIC_HITS 3
+#define TFRS_LISTWISE_METRIC_PRECISION 4
+#define TFRS_LISTWISE_METRIC_RECALL 5
+#define TFRS_LISTWISE_METRIC_MAP 6
+#define TFRS_LISTWISE_METRIC_ARP 7
+#define TFRS_LISTWISE_METRIC_OPA 8
+int tfrs_listwise_metrics(const float *labels, const float *scores, int64_t nlists, int len, int nmetrics,
+                          const int *kinds, const int *topns, float *values, float *weights, void *stream);
 /* The two pairwise kinds with LambdaRank / LambdaLoss pair weights (losses.DCGLambdaWeight / NDCGLambdaWeight; formulas:
  * DESIGN 4.25): every pair term is multiplied by
  *   w_ij = |G_i - G_j| * ((1 - smooth_fraction) * |D(r_i) - D(r_j)| + smooth_fraction * |D0(d) - D0(d + 1)|),

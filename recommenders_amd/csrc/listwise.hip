@@ -1,6 +1,7 @@
 // listwise.hip -- listwise ranking losses (softmax, pairwise logistic, pairwise hinge, ListMLE) with their gradients,
-// the two pairwise ones also with LambdaRank / LambdaLoss pair weights, and per-list NDCG, on [nlists, len] label /
-// score matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24, 4.25).
+// the two pairwise ones also with LambdaRank / LambdaLoss pair weights, and the per-list ranking metrics (NDCG, DCG, MRR,
+// hits, precision, recall, MAP, ARP, OPA: all that a step asks for out of one launch), on [nlists, len] label / score
+// matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24, 4.25, 4.26).
 //
 // Position i of a list is VALID iff label[i] >= 0 (-1 pads; a NaN label is not valid either).  Invalid positions are
 // selected out when the list is loaded -- their score is replaced by 0 and never enters any arithmetic -- and their
@@ -30,7 +31,18 @@
 //                  same scan of -lse_r in the prefix direction.  Both scans never leave the range of the scores.
 //   softmax        max, sum of exp(s - max), sum of y (lse - s), sum of y: group sums.
 //   NDCG           two sorts (by score: DCG, by label: IDCG); each a group sum over the ranks r < min(n, topn) of
-//                  (2^y - 1) / log2(r + 2).
+//                  (2^y - 1) / log2(r + 2), the thread that holds sorted slot r = sub + G c adding its ranks c = 0 .. 3
+//                  in that order.  Metrics kernel (listwise_metrics_kernel); so are the eight below.  Counts (R, c_r,
+//                  P, C, the number of positive labels) are integers: exact, their order immaterial.
+//   DCG            NDCG's numerator: the same terms, the same group sum.
+//   MRR            an integer group sum (r* + 1 at the one slot with rel and c_r = 1, r < k), one conversion, one division.
+//   hits           c_{k-1} as an integer group sum of rel over the slots r < k; no float arithmetic.
+//   precision      the same c_{k-1}; one division of two converted integers.
+//   recall         the same c_{k-1}; one division by R.
+//   MAP            c_r by ballot + popcount in the wave plus the totals of the 64-rank chunks before it; a group sum
+//                  over the relevant ranks r < k of float(c_r) / float(r + 1); one division by R.
+//   ARP            two group sums over the sorted slots, y and y * float(r + 1); one division.
+//   OPA            the pairwise walk on two integer counters per thread; integer group sums; one division.
 //   lambda weights the pairwise walk above with every term multiplied by w_ij before it is added; separate
 //                  kernels (listwise_lambda_kernel), the unweighted ones carry no trace of them.  A sort by score; the
 //                  thread at sorted slot r scatters rank r + 1 and the discount D(r + 1) to its item's position.  When
@@ -346,41 +358,239 @@ __global__ void __launch_bounds__(kLwThreads) listwise_loss_kernel(int kind, con
   }
 }
 
+// ---- ranking metrics (NDCG, DCG, MRR, hits, precision, recall, MAP, ARP, OPA; formulas: DESIGN 4.26) ---------------------
+// Every requested metric of a list out of ONE launch: the list is loaded once and sorted by score once (a second sort,
+// by label, only when some metric is NDCG; the pair walk only when some metric is OPA).  What to compute arrives as a
+// by-value descriptor -- a kernel argument, no device memory -- so every branch on it is uniform over the grid.
+enum { kLmNdcg = TFRS_LISTWISE_METRIC_NDCG, kLmDcg = TFRS_LISTWISE_METRIC_DCG, kLmMrr = TFRS_LISTWISE_METRIC_MRR,
+       kLmHits = TFRS_LISTWISE_METRIC_HITS, kLmPrecision = TFRS_LISTWISE_METRIC_PRECISION,
+       kLmRecall = TFRS_LISTWISE_METRIC_RECALL, kLmMap = TFRS_LISTWISE_METRIC_MAP, kLmArp = TFRS_LISTWISE_METRIC_ARP,
+       kLmOpa = TFRS_LISTWISE_METRIC_OPA };
+enum { kLmLabelSort = 1,   // some NDCG: the ideal order
+       kLmScoreSort = 2,   // anything but OPA
+       kLmGain = 4,        // NDCG, DCG: the terms (2^y - 1) / log2(r + 2)
+       kLmCount = 8,       // MRR, hits, precision, recall, MAP: rel, c_r, R
+       kLmArpSums = 16, kLmPairs = 32,
+       kLmPositive = 64 };   // DCG: its weight, [some label > 0]
+struct LwMetricDesc {      // (ints only: the kernel copies it to LDS word by word)
+  int n, flags;
+  int rank_lim;   // the widest cut of the metrics that read the score order: no sorted slot beyond it is looked at
+  int gain_lim;   // the widest cut of the NDCG / DCG metrics: no gain term is evaluated at a rank beyond it
+  int kind[TFRS_LISTWISE_METRIC_MAX], topn[TFRS_LISTWISE_METRIC_MAX];
+};
+
+// lw_sum on integers (exact, so its order is immaterial); the wave sums cross LDS as bit patterns.
 template <int G>
-__global__ void __launch_bounds__(kLwThreads) listwise_ndcg_kernel(const float *__restrict__ labels,
-                                                                   const float *__restrict__ scores, int64_t nlists,
-                                                                   int len, int P, int topn, float *__restrict__ ndcg,
-                                                                   float *__restrict__ counted) {
+__device__ __forceinline__ int lw_isum(int v, float *red) {
+  constexpr int W = G < 64 ? G : 64;
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if constexpr (G == 256) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __int_as_float(v);
+    __syncthreads();
+    v = __float_as_int(red[0]) + __float_as_int(red[1]) + __float_as_int(red[2]) + __float_as_int(red[3]);
+  }
+  return v;
+}
+
+template <int G>
+__global__ void __launch_bounds__(kLwThreads) listwise_metrics_kernel(const float *__restrict__ labels,
+                                                                      const float *__restrict__ scores,
+                                                                      float *__restrict__ values,
+                                                                      float *__restrict__ weights, int64_t nlists,
+                                                                      int len, int P, const LwMetricDesc d) {
   constexpr int IPT = LwCfg<G>::IPT;
+  constexpr int kWords = sizeof(LwMetricDesc) / sizeof(int);
   __shared__ LwShared<G> sh;
+  // The descriptor goes to LDS (a[1], free here) with the first loads of the kernel and is read from there: a
+  // kernel-argument read at its point of use -- in the metric loop, after the sorts -- is a trip to the argument memory
+  // that nothing overlaps, paid by every workgroup.  lw_load's barrier covers the copy.
+  if (threadIdx.x < kWords) sh.a[1][threadIdx.x] = __int_as_float(reinterpret_cast<const int *>(&d)[threadIdx.x]);
+  const float *dw = sh.a[1];
   LwList<G> l;
   lw_load<G>(l, sh, labels, scores, nlists, len);
-  const int lim = topn > 0 && topn < P ? topn : P;
-  float sums[2];
+  const int nmetrics = __float_as_int(dw[0]), flags = __float_as_int(dw[1]);
+  const int rank_lim = __float_as_int(dw[2]), gain_lim = __float_as_int(dw[3]);
+  // what the thread keeps of sorted slot r = sub + G c: ideal order (by label) and score order
+  float ti[IPT], tr[IPT], yr[IPT];     // gain terms of the two orders; the label at score rank r
+  bool oki[IPT], okr[IPT], rel[IPT];   // a valid item sits at the slot; it is relevant (y >= 1)
+  int cr[IPT];                         // c_r: relevant items at score ranks <= r
 #pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {   // 0: by score (DCG), 1: by label (IDCG)
+  for (int c = 0; c < IPT; ++c) {
+    ti[c] = tr[c] = 0.0f;
+    yr[c] = -1.0f;
+    oki[c] = okr[c] = rel[c] = false;
+    cr[c] = 0;
+  }
+
+  if (flags & kLmLabelSort) {
 #pragma unroll
     for (int c = 0; c < IPT; ++c) {
       const int i = l.sub + G * c;
-      sh.key[l.off + i] = l.valid[c] ? make_key(pass == 0 ? l.sv[c] : l.yv[c], i) : 0ull;
+      sh.key[l.off + i] = l.valid[c] ? make_key(l.yv[c], i) : 0ull;
     }
     __syncthreads();
     lw_sort<G>(l, sh, P);
-    float t = 0.0f;
 #pragma unroll
     for (int c = 0; c < IPT; ++c) {
       const int r = l.sub + G * c;
-      const uint64_t k = r < lim ? sh.key[l.off + r] : 0ull;
-      if (k != 0ull) t += (exp2f(sh.y[l.off + key_index(k)]) - 1.0f) / log2f((float)(r + 2));
+      const uint64_t k = r < P && r < gain_lim ? sh.key[l.off + r] : 0ull;
+      oki[c] = k != 0ull;
+      if (oki[c]) ti[c] = (exp2f(sh.y[l.off + key_index(k)]) - 1.0f) / log2f((float)(r + 2));
     }
-    sums[pass] = lw_sum<G>(t, sh.red);
     __syncthreads();
   }
-  if (l.active && l.sub == 0) {
-    const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
-    const bool cnt = sums[1] > 0.0f;
-    ndcg[list] = cnt ? sums[0] / sums[1] : 0.0f;
-    counted[list] = cnt ? 1.0f : 0.0f;
+
+  int nrel = 0, npos = 0;              // R; the number of valid labels > 0
+  float ysum = 0.0f, ynum = 0.0f;      // ARP: sum_V y, sum_V y (r + 1)
+  if (flags & kLmScoreSort) {
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      sh.key[l.off + i] = l.valid[c] ? make_key(l.sv[c], i) : 0ull;
+    }
+    __syncthreads();
+    lw_sort<G>(l, sh, P);
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int r = l.sub + G * c;
+      const uint64_t k = r < P && r < rank_lim ? sh.key[l.off + r] : 0ull;
+      okr[c] = k != 0ull;
+      if (okr[c]) {
+        yr[c] = sh.y[l.off + key_index(k)];
+        rel[c] = yr[c] >= 1.0f;
+        if ((flags & kLmGain) && r < gain_lim) tr[c] = (exp2f(yr[c]) - 1.0f) / log2f((float)(r + 2));
+      }
+    }
+    if (flags & kLmPositive) {
+      int t = 0;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) t += l.valid[c] && l.yv[c] > 0.0f ? 1 : 0;
+      npos = lw_isum<G>(t, sh.red);
+    }
+    if (flags & kLmCount) {
+      // c_r: ballot + popcount inside the wave (a group of G < 64 lanes reads its own bits of the mask); at G = 256
+      // slot r lies in 64-rank chunk 4 c + wave, and the 16 chunk totals cross LDS (in m[0], free here)
+      const int lane = threadIdx.x & 63;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const uint64_t mask = __ballot(rel[c]);
+        if constexpr (G == 256) {
+          cr[c] = __popcll(mask & ((2ull << lane) - 1ull));
+          if (lane == 0) sh.m[0][4 * c + (threadIdx.x >> 6)] = __int_as_float(__popcll(mask));
+        } else if constexpr (G == 64) {
+          cr[c] = __popcll(mask & ((2ull << lane) - 1ull));
+        } else {
+          const uint64_t mine = (mask >> (lane / G * G)) & ((1ull << G) - 1ull);
+          cr[c] = __popcll(mine & ((2ull << l.sub) - 1ull));
+        }
+      }
+      if constexpr (G == 256) {
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < IPT; ++c) {
+          const int q = 4 * c + (threadIdx.x >> 6);
+          int before = 0;
+#pragma unroll
+          for (int p = 0; p < 4 * IPT - 1; ++p) before += p < q ? __float_as_int(sh.m[0][p]) : 0;
+          cr[c] += before;
+        }
+      }
+      int t = 0;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) t += l.valid[c] && l.yv[c] >= 1.0f ? 1 : 0;      // (own items: every rank counts)
+      nrel = lw_isum<G>(t, sh.red);
+    }
+    if (flags & kLmArpSums) {
+      float t = 0.0f, u = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        if (okr[c]) {
+          t += yr[c];
+          u += yr[c] * (float)(l.sub + G * c + 1);
+        }
+      }
+      ysum = lw_sum<G>(t, sh.red);
+      ynum = lw_sum<G>(u, sh.red);
+    }
+  }
+
+  int npairs = 0, nright = 0;          // OPA: P and C
+  if (flags & kLmPairs) {            // the broadcast j loop of lw_pairs, on integer counts
+    int pc = 0, cc = 0;
+    for (int j = 0; j < len; ++j) {
+      const float yj = sh.y[l.off + j], sj = sh.s[l.off + j];
+      if (!(yj >= 0.0f)) continue;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        if (l.valid[c] && l.yv[c] > yj) {
+          ++pc;
+          cc += l.sv[c] > sj ? 1 : 0;
+        }
+      }
+    }
+    npairs = lw_isum<G>(pc, sh.red);
+    nright = lw_isum<G>(cc, sh.red);
+  }
+
+  const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
+  for (int m = 0; m < nmetrics; ++m) {
+    const int kind = __float_as_int(dw[4 + m]), topn = __float_as_int(dw[4 + TFRS_LISTWISE_METRIC_MAX + m]);
+    const int lim = topn > 0 && topn < P ? topn : P;      // rank r is inside the cut iff r < lim and a valid item is there
+    float v = 0.0f, w = 0.0f;
+    if (kind == kLmNdcg || kind == kLmDcg) {
+      float t = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (okr[c] && l.sub + G * c < lim) t += tr[c];
+      const float dcg = lw_sum<G>(t, sh.red);
+      if (kind == kLmNdcg) {
+        t = 0.0f;
+#pragma unroll
+        for (int c = 0; c < IPT; ++c) if (oki[c] && l.sub + G * c < lim) t += ti[c];
+        const float idcg = lw_sum<G>(t, sh.red);
+        const bool cnt = idcg > 0.0f;
+        v = cnt ? dcg / idcg : 0.0f;
+        w = cnt ? 1.0f : 0.0f;
+      } else {
+        w = npos > 0 ? 1.0f : 0.0f;
+        v = npos > 0 ? dcg : 0.0f;
+      }
+    } else if (kind == kLmMrr) {
+      int t = 0;                                           // r* + 1 at the one slot that holds the first relevant item
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (rel[c] && cr[c] == 1 && l.sub + G * c < lim) t += l.sub + G * c + 1;
+      const int first = lw_isum<G>(t, sh.red);
+      w = nrel > 0 ? 1.0f : 0.0f;
+      v = first > 0 ? 1.0f / (float)first : 0.0f;
+    } else if (kind == kLmHits || kind == kLmPrecision || kind == kLmRecall) {
+      int t = 0;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) t += rel[c] && l.sub + G * c < lim ? 1 : 0;
+      const int ck = lw_isum<G>(t, sh.red);                // c_{k - 1}
+      w = nrel > 0 ? 1.0f : 0.0f;
+      if (kind == kLmHits) v = ck > 0 ? 1.0f : 0.0f;
+      else if (kind == kLmPrecision) v = (float)ck / (float)(topn > 0 && topn < len ? topn : len);
+      else v = nrel > 0 ? (float)ck / (float)nrel : 0.0f;
+    } else if (kind == kLmMap) {
+      float t = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c)
+        if (rel[c] && l.sub + G * c < lim) t += (float)cr[c] / (float)(l.sub + G * c + 1);
+      const float ap = lw_sum<G>(t, sh.red);
+      w = nrel > 0 ? 1.0f : 0.0f;
+      v = nrel > 0 ? ap / (float)nrel : 0.0f;
+    } else if (kind == kLmArp) {
+      w = ysum > 0.0f ? ysum : 0.0f;
+      v = ysum > 0.0f ? ynum / ysum : 0.0f;
+    } else {   // OPA
+      w = (float)npairs;
+      v = npairs > 0 ? (float)nright / (float)npairs : 0.0f;
+    }
+    if (l.active && l.sub == 0) {
+      values[(int64_t)m * nlists + list] = v;
+      weights[(int64_t)m * nlists + list] = w;
+    }
   }
 }
 
@@ -553,7 +763,7 @@ static int lw_check_shape(const char *what, int64_t nlists, int len) {
 
 #define TFRS_LW_FWD(G) listwise_loss_kernel<G, false>
 #define TFRS_LW_BWD(G) listwise_loss_kernel<G, true>
-#define TFRS_LW_NDCG(G) listwise_ndcg_kernel<G>
+#define TFRS_LW_METRICS(G) listwise_metrics_kernel<G>
 #define TFRS_LW_LAMBDA_FWD(G) listwise_lambda_kernel<G, false, false>
 #define TFRS_LW_LAMBDA_FWD_SMOOTH(G) listwise_lambda_kernel<G, false, true>
 #define TFRS_LW_LAMBDA_BWD(G) listwise_lambda_kernel<G, true, false>
@@ -565,6 +775,36 @@ static int lw_check_lambda(const char *what, int kind, int topn, float smooth_fr
   TFRS_CHECK_ARG(topn >= 0, "%s: topn=%d must be positive, or 0 for no cut", what, topn);
   TFRS_CHECK_ARG(smooth_fraction >= 0.0f && smooth_fraction <= 1.0f, "%s: smooth_fraction=%g outside [0, 1]", what,
                  (double)smooth_fraction);
+  return TFRS_OK;
+}
+
+// One launch for validated arguments: the descriptor is built here, on the host, and travels as a kernel argument.
+static int lw_launch_metrics(const float *labels, const float *scores, int64_t nlists, int len, int nmetrics,
+                             const int *kinds, const int *topns, float *values, float *weights, hipStream_t s) {
+  LwMetricDesc d = {};
+  d.n = nmetrics;
+  for (int m = 0; m < nmetrics; ++m) {
+    const int k = kinds[m];
+    d.kind[m] = k;
+    d.topn[m] = topns[m];
+    if (k != kLmOpa) {
+      d.flags |= kLmScoreSort;
+      const int cut = topns[m] > 0 ? topns[m] : kLwMaxLen;
+      d.rank_lim = cut > d.rank_lim ? cut : d.rank_lim;
+    }
+    if (k == kLmNdcg) d.flags |= kLmLabelSort;
+    if (k == kLmNdcg || k == kLmDcg) {
+      d.flags |= kLmGain;
+      const int cut = topns[m] > 0 ? topns[m] : kLwMaxLen;
+      d.gain_lim = cut > d.gain_lim ? cut : d.gain_lim;
+    }
+    if (k == kLmDcg) d.flags |= kLmPositive;
+    if (k == kLmMrr || k == kLmHits || k == kLmPrecision || k == kLmRecall || k == kLmMap) d.flags |= kLmCount;
+    if (k == kLmArp) d.flags |= kLmArpSums;
+    if (k == kLmOpa) d.flags |= kLmPairs;
+  }
+  TFRS_LW_DISPATCH(TFRS_LW_METRICS, labels, scores, values, weights, nlists, len, P, d);
+  TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
 
@@ -603,10 +843,25 @@ extern "C" int tfrs_listwise_ndcg(const float *labels, const float *scores, int6
   if (int rc = lw_check_shape("listwise_ndcg", nlists, len)) return rc;
   if (nlists == 0) return TFRS_OK;
   TFRS_CHECK_ARG(labels && scores && ndcg && counted, "listwise_ndcg: NULL pointer");
-  hipStream_t s = (hipStream_t)stream;
-  TFRS_LW_DISPATCH(TFRS_LW_NDCG, labels, scores, nlists, len, P, topn, ndcg, counted);
-  TFRS_LAUNCH_CHECK();
-  return TFRS_OK;
+  const int kind = kLmNdcg;            // the one-metric call of the metrics kernel: values = ndcg, weights = counted
+  return lw_launch_metrics(labels, scores, nlists, len, 1, &kind, &topn, ndcg, counted, (hipStream_t)stream);
+}
+
+extern "C" int tfrs_listwise_metrics(const float *labels, const float *scores, int64_t nlists, int len, int nmetrics,
+                                     const int *kinds, const int *topns, float *values, float *weights, void *stream) {
+  TFRS_CHECK_ARG(nmetrics >= 1 && nmetrics <= TFRS_LISTWISE_METRIC_MAX, "listwise_metrics: nmetrics=%d outside 1 .. %d",
+                 nmetrics, TFRS_LISTWISE_METRIC_MAX);
+  TFRS_CHECK_ARG(kinds && topns, "listwise_metrics: NULL kinds / topns array");
+  for (int m = 0; m < nmetrics; ++m) {
+    TFRS_CHECK_ARG(kinds[m] >= kLmNdcg && kinds[m] <= kLmOpa, "listwise_metrics: unknown kind %d (metric %d)", kinds[m], m);
+    TFRS_CHECK_ARG(topns[m] >= 0, "listwise_metrics: topn=%d must be positive, or 0 for no cut (metric %d)", topns[m], m);
+    TFRS_CHECK_ARG(topns[m] == 0 || (kinds[m] != kLmArp && kinds[m] != kLmOpa),
+                   "listwise_metrics: ARP and OPA take no topn, got %d (metric %d)", topns[m], m);
+  }
+  if (int rc = lw_check_shape("listwise_metrics", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && values && weights, "listwise_metrics: NULL pointer");
+  return lw_launch_metrics(labels, scores, nlists, len, nmetrics, kinds, topns, values, weights, (hipStream_t)stream);
 }
 
 extern "C" int tfrs_listwise_lambda_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,

@@ -6,13 +6,17 @@ constructor and ``call`` arguments.  ``loss`` defaults to binary cross-entropy (
 Listwise ranking (the reference's listwise tutorial) needs nothing else from the task: with ``labels`` and
 ``predictions`` of shape ``[batch, list]`` (``-1`` labels pad a list) pass ``loss=losses.SoftmaxLoss()``,
 ``PairwiseLogisticLoss()``, ``PairwiseHingeLoss()`` or ``ListMLELoss()`` and ``metrics=[metrics.NDCGMetric(topn=...)]``;
-``sample_weight`` is then one weight per list."""
+``sample_weight`` is then one weight per list.  The other list metrics go the same way (``MRRMetric``, ``HitsMetric``,
+``PrecisionMetric``, ``RecallMetric``, ``MeanAveragePrecisionMetric``, ``DCGMetric``, ``ARPMetric``, ``OPAMetric``); when
+two or more of ``metrics`` are list metrics the task updates them together, from one kernel launch that loads and sorts
+every list once (``metrics.update_listwise_metrics``), and everything else one by one as before."""
 
 from typing import Callable, List, Optional
 
 import torch
 
 from recommenders_amd import losses
+from recommenders_amd.metrics import listwise as listwise_metrics
 from recommenders_amd.tasks import base
 
 
@@ -42,8 +46,14 @@ class Ranking(torch.nn.Module, base.Task):
     if not compute_metrics:                                                              # :95-96
       return loss
     with torch.no_grad():
+      grouped = [m for m in self._ranking_metrics if isinstance(m, listwise_metrics._ListMetric)]
+      # two or more list metrics: one launch for all of them (a single one, or one listed twice, goes its own way)
+      together = len(grouped) >= 2 and len({id(m) for m in grouped}) == len(grouped)
+      if together:
+        listwise_metrics.update_listwise_metrics(grouped, labels, predictions, sample_weight=sample_weight)
       for metric in self._ranking_metrics:                                               # :100-102
-        metric.update_state(labels, predictions, sample_weight=sample_weight)
+        if not together or not isinstance(metric, listwise_metrics._ListMetric):
+          metric.update_state(labels, predictions, sample_weight=sample_weight)
       for metric in self._prediction_metrics:                                            # :104-106
         metric.update_state(predictions, sample_weight=sample_weight)
       for metric in self._label_metrics:                                                 # :108-110
