@@ -641,6 +641,52 @@ int tfrs_inbatch_softmax_mh_ce_bwd(const float *q, const float *c, int64_t nq, i
 int tfrs_inbatch_softmax_plan_f32(int64_t nq, int heads, int64_t nc, int64_t *out);
 int tfrs_inbatch_softmax_plan_f16(int64_t nq, int64_t nc, int64_t *out);
 
+/* ------------------------------------------------------------------------- *
+ * Hard-negative mining (layers/loss.py:61-111), the cross-entropy on the mined logits (tasks/retrieval.py:205-210)
+ * and the batch metrics' rank count (:228-232) over ADJUSTED in-batch logits of 2-D queries, without the [nq, nc]
+ * matrix.  These entry points take the TEMPERATURE itself (1 for none), not its reciprocal:
+ *   S_bc = (q_b . c_c) / temperature - log_q_correction_c [+ MIN_FLOAT where cand_ids[c] == cand_ids[b], c != b]
+ *          [= MIN_FLOAT where !score_mask_bc]     IEEE f32 division, as the reference's scores / temperature;
+ *                                                  -0 counts as +0; non-finite embeddings are outside the contract
+ *   keep(b, c) = (c == b) || S_bc > tau_b || (S_bc == tau_b && c <= cut_b)
+ *   tfrs_inbatch_mined_select: with n = min(num_hard_negatives, nc - 1), tau[b] = the n-th largest negative logit of
+ *     row b and cut[b] = the column of the last tied negative that is taken (INT64_MAX: all ties) -- the kept set is
+ *     the positive and the n largest negatives, equal values going to the lower column (tf.math.top_k).  n = 0:
+ *     tau = +inf, cut = -1.  Exact (a radix select on the device), a fixed launch sequence: capturable.
+ *   tfrs_inbatch_mined_ce_fwd: loss = sum_b w_b (logsumexp_{c : keep(b, c)} S_bc - S_bb); out_lse[nq], out_pos[nq].
+ *   tfrs_inbatch_mined_ce_bwd: G_bc = gloss * w_b * (exp(S_bc - lse_b) - [b == c]) / temperature where keep(b, c)
+ *     and not masked, 0 elsewhere; dq = G c, dc = G^T q.  Deterministic, no float atomics.
+ *   tfrs_inbatch_mined_rank_count: counts[b] = #{c != b : keep(b, c) and S_bc > S_bb}, bit 31 set for a non-finite
+ *     S_bb: the uint32 counts[nq] convention of tfrs_rank_count_accumulate, consumed by tfrs_topk_hits_update.
+ *   tau / cut of the last three: both NULL keeps every column (adjustments without mining).
+ * Optional inputs (sample_weight, log_q_correction = log clip(p, 1e-6, 1), cand_ids, score_mask) may be NULL.
+ * TFRS_EINVAL before any device call: a shape below 1, nc < nq, d > TFRS_MAX_DIM, a NULL operand / output /
+ * workspace, a temperature that is zero or not finite, num_hard_negatives < 0, tau without cut, a workspace below
+ * tfrs_inbatch_mined_workspace_bytes (one size for the four calls, each of which overwrites it).
+ *   tfrs_inbatch_mined_plan (host only): out[4] = {nsplit, split_len} of the kernels that stream candidates
+ *     (selection, forward, count, dq), then of dc (streams queries), under TFRS_SOFTMAX_WAVES.
+ * ------------------------------------------------------------------------- */
+size_t tfrs_inbatch_mined_workspace_bytes(int64_t nq, int64_t nc, int d);
+int tfrs_inbatch_mined_plan(int64_t nq, int64_t nc, int64_t *out);
+int tfrs_inbatch_mined_select(const float *q, const float *c, int64_t nq, int64_t nc, int d, float temperature,
+                              const float *log_q_correction, const int64_t *cand_ids, const uint8_t *score_mask,
+                              int64_t num_hard_negatives, float *tau, int64_t *cut, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int tfrs_inbatch_mined_ce_fwd(const float *q, const float *c, int64_t nq, int64_t nc, int d,
+                              const float *sample_weight, float temperature, const float *log_q_correction,
+                              const int64_t *cand_ids, const uint8_t *score_mask, const float *tau,
+                              const int64_t *cut, float *out_loss, float *out_lse, float *out_pos, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int tfrs_inbatch_mined_ce_bwd(const float *q, const float *c, int64_t nq, int64_t nc, int d,
+                              const float *sample_weight, float temperature, const float *log_q_correction,
+                              const int64_t *cand_ids, const uint8_t *score_mask, const float *tau,
+                              const int64_t *cut, const float *lse, const float *gloss, float *dq, float *dc,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int tfrs_inbatch_mined_rank_count(const float *q, const float *c, int64_t nq, int64_t nc, int d, float temperature,
+                                  const float *log_q_correction, const int64_t *cand_ids, const uint8_t *score_mask,
+                                  const float *tau, const int64_t *cut, uint32_t *counts, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 /* Multi-head exact top-K (BruteForce on queries [nq, heads, d]): scores / rows [nq, heads, k_in] are the top-k_in
  * lists of the nq * heads flat (query, head) rows (descending; row < 0 = empty).  Writes, per query, the top-k_out
  * of max_h score under (score descending, row ascending): a row that appears in several lists counts once, with

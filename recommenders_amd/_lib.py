@@ -128,6 +128,14 @@ SIGNATURES = {
                                                P, P, P, P, P, c_size_t, P]),
     "tfrs_inbatch_softmax_plan_f32": (c_int, [c_i64, c_int, c_i64, P]),
     "tfrs_inbatch_softmax_plan_f16": (c_int, [c_i64, c_i64, P]),
+    "tfrs_inbatch_mined_workspace_bytes": (c_size_t, [c_i64, c_i64, c_int]),
+    "tfrs_inbatch_mined_plan": (c_int, [c_i64, c_i64, P]),
+    "tfrs_inbatch_mined_select": (c_int, [P, P, c_i64, c_i64, c_int, c_float, P, P, P, c_i64, P, P, P, c_size_t, P]),
+    "tfrs_inbatch_mined_ce_fwd": (c_int, [P, P, c_i64, c_i64, c_int, P, c_float, P, P, P, P, P,
+                                          P, P, P, P, c_size_t, P]),
+    "tfrs_inbatch_mined_ce_bwd": (c_int, [P, P, c_i64, c_i64, c_int, P, c_float, P, P, P, P, P,
+                                          P, P, P, P, P, c_size_t, P]),
+    "tfrs_inbatch_mined_rank_count": (c_int, [P, P, c_i64, c_i64, c_int, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     "tfrs_topk_merge_heads": (c_int, [P, P, c_i64, c_int, c_int, c_int, P, P, P]),
     "tfrs_logits_ce_fwd": (c_int, [P, P, c_i64, c_i64, P, P, P, P, P]),
     "tfrs_logits_ce_bwd": (c_int, [P, P, c_i64, c_i64, P, P, P, P, P, P]),

@@ -40,6 +40,7 @@ SOURCES = [
     "hashing.hip",
     "softmax.hip",
     "softmax16.hip",
+    "softmax_mined.hip",
     "logits_ce.hip",
     "listwise.hip",
     "interaction.hip",

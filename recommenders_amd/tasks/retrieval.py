@@ -8,17 +8,22 @@ Mirror of ``tensorflow_recommenders/tasks/retrieval.py:29-235``: same constructo
 temperature (:187), sampling-probability correction (:190), accidental-hit removal
 (:194-200) and ``score_mask`` (:202) folded into the logit function.
 
-``batch_metrics`` (:228-232) of unadjusted logits are updated from rank counts
-(``TopKCategoricalAccuracy.update_from_embeddings``) and ``num_hard_negatives`` (:205-208) over
-plain dot-product logits from the fused top-K search (``hard_negative_softmax_loss``): neither
-builds the ``[num_queries, num_candidates]`` matrix.  Multi-head (3-D, max-sim) queries (:173-176)
+``batch_metrics`` (:228-232) are updated from rank counts -- of the plain dot products
+(``TopKCategoricalAccuracy.update_from_embeddings``) or of the adjusted / mined logits the loss saw
+(``update_from_adjusted``: the temperature divides there as in the reference).  ``num_hard_negatives`` (:205-208) over
+plain dot-product logits takes the fused top-K search (``hard_negative_softmax_loss``); every other hard-negative
+configuration of the built-in loss -- a sampling correction, accidental-hit removal, a score mask, batch metrics, any
+``num_hard_negatives`` -- takes ``mined_in_batch_softmax_loss``: an exact radix select per row and a keep predicate
+inside the streaming kernels (``tfrs_inbatch_mined_*``).  None of these builds the ``[num_queries, num_candidates]``
+matrix.  Multi-head (3-D, max-sim) queries (:173-176)
 with up to 32 heads take the same fused route (``tfrs_inbatch_softmax_mh_ce_fwd/_bwd``: the max over
 heads is taken inside the kernels, the gradient of a pair goes to its lowest maximal head).  What
-still needs the explicit matrix -- a user-supplied ``loss`` (its contract IS the matrix), batch
-metrics / hard negatives combined with a logit adjustment that can reorder a row (temperature for
-the metrics, sampling correction, accidental-hit removal, score mask), and multi-head queries
+still needs the explicit matrix -- a user-supplied ``loss`` (its contract IS the matrix), embedding dims above 128,
+more queries than candidates, foreign batch-metric classes, and multi-head queries
 combined with hard negatives, batch metrics or more than 32 heads -- computes it with the HIP dense
-GEMM and then follows the reference's op sequence on that tensor.
+GEMM and then follows the reference's op sequence on that tensor.  ``TFRS_RETRIEVAL_EXPLICIT=1`` (read per call) sends
+hard negatives / batch metrics over adjusted logits back to that route: the comparator of tests and
+``tools/bench_hard_negatives.py``.
 """
 
 import os
@@ -95,11 +100,8 @@ class _InBatchSoftmaxFn(torch.autograd.Function):
     return dq, dc, None, None, None, None, None
 
 
-def _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, temperature,
-                        candidate_sampling_probability, candidate_ids, score_mask):
-  """Turns the options of the two public functions into the device tensors of the kernels and runs them."""
-  dev = query_embeddings.device
-  inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
+def _logit_options(dev, sample_weight, candidate_sampling_probability, candidate_ids, score_mask):
+  """The device tensors the fused kernels take for the logit options: ``(w, log clip(p), ids, mask)``, None where unset."""
   w = None if sample_weight is None else sample_weight.reshape(-1).to(dev, torch.float32).contiguous()
   corr = None
   if candidate_sampling_probability is not None:                      # loss.py:157-158
@@ -107,6 +109,15 @@ def _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, t
                                  1e-6, 1.0)).contiguous()
   ids = None if candidate_ids is None else candidate_ids.reshape(-1).to(dev).long().contiguous()
   mask = None if score_mask is None else score_mask.to(dev).to(torch.uint8).contiguous()
+  return w, corr, ids, mask
+
+
+def _fused_softmax_loss(query_embeddings, candidate_embeddings, sample_weight, temperature,
+                        candidate_sampling_probability, candidate_ids, score_mask):
+  """Turns the options of the two public functions into the device tensors of the kernels and runs them."""
+  inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
+  w, corr, ids, mask = _logit_options(query_embeddings.device, sample_weight, candidate_sampling_probability,
+                                      candidate_ids, score_mask)
   return _InBatchSoftmaxFn.apply(query_embeddings.to(torch.float32),
                                  candidate_embeddings.to(torch.float32), w, inv_t, corr, ids, mask)
 
@@ -182,6 +193,86 @@ def hard_negative_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddi
   if sample_weight is not None:
     per_row = per_row * sample_weight.reshape(-1).to(per_row.device, torch.float32)
   return per_row.sum()                                                   # Reduction.SUM (:86-87)
+
+
+class _MinedSoftmaxFn(torch.autograd.Function):
+  """``(loss, tau, cut)`` of the mined in-batch softmax (``tfrs_inbatch_mined_select`` / ``_ce_fwd`` / ``_ce_bwd``):
+  the kept set of row ``b`` is its positive and the ``n`` negatives with the largest adjusted logits, written as the
+  threshold ``tau[b]`` and the cut column ``cut[b]`` that the metric count reuses.  Only the loss is differentiable."""
+
+  @staticmethod
+  def _workspace(lib, q, c):
+    return torch.empty((lib.tfrs_inbatch_mined_workspace_bytes(q.shape[0], c.shape[0], q.shape[1]),),
+                       dtype=torch.uint8, device=q.device)
+
+  @staticmethod
+  def forward(ctx, q, c, sample_weight, temperature, log_corr, cand_ids, score_mask, num_hard_negatives):
+    lib = _lib.load()
+    q = q.contiguous()
+    c = c.contiguous()
+    (nq, d), nc = q.shape, c.shape[0]
+    ws = _MinedSoftmaxFn._workspace(lib, q, c)
+    tau = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    cut = torch.empty((nq,), dtype=torch.int64, device=q.device)
+    loss = torch.empty((), dtype=torch.float32, device=q.device)
+    lse = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    pos = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    stream = _lib.current_stream()
+    _lib.check(lib.tfrs_inbatch_mined_select(
+        _lib.ptr(q), _lib.ptr(c), nq, nc, d, float(temperature), _lib.ptr(log_corr), _lib.ptr(cand_ids),
+        _lib.ptr(score_mask), int(num_hard_negatives), _lib.ptr(tau), _lib.ptr(cut), _lib.ptr(ws), ws.numel(), stream))
+    _lib.check(lib.tfrs_inbatch_mined_ce_fwd(
+        _lib.ptr(q), _lib.ptr(c), nq, nc, d, _lib.ptr(sample_weight), float(temperature), _lib.ptr(log_corr),
+        _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(tau), _lib.ptr(cut), _lib.ptr(loss), _lib.ptr(lse),
+        _lib.ptr(pos), _lib.ptr(ws), ws.numel(), stream))
+    ctx.save_for_backward(q, c, sample_weight, log_corr, cand_ids, score_mask, tau, cut, lse)
+    ctx.temperature = float(temperature)
+    ctx.mark_non_differentiable(tau, cut)
+    return loss, tau, cut
+
+  @staticmethod
+  def backward(ctx, gloss, _gtau, _gcut):
+    q, c, sample_weight, log_corr, cand_ids, score_mask, tau, cut, lse = ctx.saved_tensors
+    lib = _lib.load()
+    dq = torch.empty_like(q)
+    dc = torch.empty_like(c)
+    g = gloss.to(torch.float32).contiguous()
+    ws = _MinedSoftmaxFn._workspace(lib, q, c)
+    _lib.check(lib.tfrs_inbatch_mined_ce_bwd(
+        _lib.ptr(q), _lib.ptr(c), q.shape[0], c.shape[0], q.shape[1], _lib.ptr(sample_weight), ctx.temperature,
+        _lib.ptr(log_corr), _lib.ptr(cand_ids), _lib.ptr(score_mask), _lib.ptr(tau), _lib.ptr(cut), _lib.ptr(lse),
+        _lib.ptr(g), _lib.ptr(dq), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+    return dq, dc, None, None, None, None, None, None
+
+
+def _mined_softmax(query_embeddings, candidate_embeddings, num_hard_negatives, sample_weight, temperature,
+                   candidate_sampling_probability, candidate_ids, score_mask):
+  """``(loss, tau, cut)``: see ``mined_in_batch_softmax_loss``."""
+  if query_embeddings.dim() != 2:
+    raise ValueError(f"queries must be [B, D] (got {tuple(query_embeddings.shape)}).")
+  if int(num_hard_negatives) < 0:
+    raise ValueError(f"num_hard_negatives must not be negative (got {num_hard_negatives}).")
+  w, corr, ids, mask = _logit_options(query_embeddings.device, sample_weight, candidate_sampling_probability,
+                                      candidate_ids, score_mask)
+  return _MinedSoftmaxFn.apply(query_embeddings.to(torch.float32), candidate_embeddings.to(torch.float32), w,
+                               1.0 if temperature is None else float(temperature), corr, ids, mask,
+                               int(num_hard_negatives))
+
+
+def mined_in_batch_softmax_loss(query_embeddings: torch.Tensor, candidate_embeddings: torch.Tensor,
+                                num_hard_negatives: int, sample_weight: Optional[torch.Tensor] = None,
+                                temperature: Optional[float] = None,
+                                candidate_sampling_probability: Optional[torch.Tensor] = None,
+                                candidate_ids: Optional[torch.Tensor] = None,
+                                score_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """``HardNegativeMining`` + softmax cross-entropy (layers/loss.py:61-111, tasks/retrieval.py:205-210) over the
+  ADJUSTED logits of :178-203 -- temperature (an IEEE division, as the reference's), sampling-probability correction,
+  accidental-hit removal (``candidate_ids``), ``score_mask`` -- without the ``[B, C]`` matrix and for any
+  ``num_hard_negatives``: an exact radix select on the device finds, per row, the threshold of its
+  ``min(num_hard_negatives, C - 1)`` largest negatives (equal values go to the lower column, ``tf.math.top_k``'s
+  rule), the loss kernels stream the candidates again and keep what passes it.  ``D <= 128``, ``C >= B``."""
+  return _mined_softmax(query_embeddings, candidate_embeddings, num_hard_negatives, sample_weight, temperature,
+                        candidate_sampling_probability, candidate_ids, score_mask)[0]
 
 
 class _CrossReplicaConcatFn(torch.autograd.Function):
@@ -262,6 +353,33 @@ class TopKCategoricalAccuracy:
     _lib.check(lib.tfrs_rank_count_accumulate(
         _lib.ptr(q), _lib.ptr(c), nq, d, _lib.ptr(c), None, 0, c.shape[0], c.shape[0], _lib.ptr(counts), 1,
         stream))
+    ks = (ctypes.c_int32 * 1)(int(self.k))
+    _lib.check(lib.tfrs_topk_hits_update(_lib.ptr(counts), nq, ks, 1, None, _lib.ptr(scratch),
+                                         _lib.ptr(scratch[2:]), _lib.ptr(hits), stream))
+    self._mean.update_state(hits[0], sample_weight)
+
+  def update_from_adjusted(self, q: torch.Tensor, c: torch.Tensor, sample_weight=None, temperature=None,
+                           candidate_sampling_probability=None, candidate_ids=None, score_mask=None,
+                           tau=None, cut=None) -> None:
+    """The same update on the ADJUSTED logits the loss saw (:178-208), still without the matrix:
+    ``tfrs_inbatch_mined_rank_count`` re-scores the batch with the temperature division, the sampling correction,
+    accidental-hit removal and the score mask applied in registers and counts, per row, the kept negatives strictly
+    above the positive.  ``tau`` / ``cut``: the kept set of the mined loss (``None``: every column is kept)."""
+    import ctypes
+    lib = _lib.load()
+    nq, d = q.shape
+    q = q.detach().to(torch.float32).contiguous()
+    c = c.detach().to(torch.float32).contiguous()
+    _, corr, ids, mask = _logit_options(q.device, None, candidate_sampling_probability, candidate_ids, score_mask)
+    counts = torch.empty((nq,), dtype=torch.int32, device=q.device)
+    hits = torch.empty((1, nq), dtype=torch.float32, device=q.device)
+    scratch = torch.zeros((3,), dtype=torch.float32, device=q.device)     # state[2], result[1] (unused)
+    ws = _MinedSoftmaxFn._workspace(lib, q, c)
+    stream = _lib.current_stream()
+    _lib.check(lib.tfrs_inbatch_mined_rank_count(
+        _lib.ptr(q), _lib.ptr(c), nq, c.shape[0], d, 1.0 if temperature is None else float(temperature),
+        _lib.ptr(corr), _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(tau), _lib.ptr(cut), _lib.ptr(counts), _lib.ptr(ws),
+        ws.numel(), stream))
     ks = (ctypes.c_int32 * 1)(int(self.k))
     _lib.check(lib.tfrs_topk_hits_update(_lib.ptr(counts), nq, ks, 1, None, _lib.ptr(scratch),
                                          _lib.ptr(scratch[2:]), _lib.ptr(hits), stream))
@@ -434,45 +552,63 @@ class Retrieval(torch.nn.Module, base.Task):
     # the fused kernels hold an embedding row in registers: dims above 128 (outside their
     # envelope; the reference accepts any dim) take the explicit-logits path below
     wide = q.dim() == 2 and q.shape[-1] > 128
+    has_batch_metrics = compute_batch_metrics and len(self._batch_metrics) > 0
+    adjusted = (self._temperature is not None or candidate_sampling_probability is not None
+                or self._remove_accidental_hits or score_mask is not None)
+    # TFRS_RETRIEVAL_EXPLICIT=1 (read per call: tests and tools/bench_hard_negatives.py switch it) keeps hard
+    # negatives / batch metrics over adjusted logits on the explicit [B, C] matrix, the comparator of the mined route
+    mined_ok = (os.environ.get("TFRS_RETRIEVAL_EXPLICIT") != "1" and self._loss is None and q.dim() == 2
+                and not wide and c.shape[0] >= q.shape[0])
+    counted_metrics = has_batch_metrics and all(type(m) is TopKCategoricalAccuracy for m in self._batch_metrics)
     # batch metrics of unadjusted logits need a rank count per row, not the matrix (missing item 3 of
-    # round 3's review): only logit adjustments that can reorder a row -- a temperature (its division
-    # can merge near-ties), the sampling correction, accidental-hit removal, a score mask, hard-negative
-    # mining -- or a foreign metric class keep them on the explicit-logits path
+    # round 3's review): tfrs_rank_count_accumulate on the plain dot products
     fused_batch_metrics = (
-        compute_batch_metrics and len(self._batch_metrics) > 0 and q.dim() == 2 and not wide
-        and self._loss is None and self._num_hard_negatives is None and self._temperature is None
-        and candidate_sampling_probability is None and not self._remove_accidental_hits
-        and score_mask is None
-        and all(type(m) is TopKCategoricalAccuracy for m in self._batch_metrics))
+        counted_metrics and q.dim() == 2 and not wide and self._loss is None
+        and self._num_hard_negatives is None and not adjusted)
     # hard-negative mining over plain (temperature-scaled) dot products: the top-K search names the rows
     fused_hard_negatives = (
         self._num_hard_negatives is not None and self._loss is None and q.dim() == 2 and not wide
         and candidate_sampling_probability is None and not self._remove_accidental_hits
         and score_mask is None and int(self._num_hard_negatives) + 2 <= 1024
-        and not (compute_batch_metrics and len(self._batch_metrics) > 0))
+        and not has_batch_metrics)
+    # every other hard-negative configuration of the built-in loss: the radix select and the keep predicate inside
+    # the streaming kernels (mined_in_batch_softmax_loss) -- unless a foreign batch metric needs the matrix anyway
+    mined_hard_negatives = (
+        self._num_hard_negatives is not None and not fused_hard_negatives and mined_ok
+        and (counted_metrics or not has_batch_metrics))
+    # ... and batch metrics of ADJUSTED (or mined) logits: the rank count over the same logit function; the
+    # temperature divides there as in the reference, so near-ties merge as they do on the matrix
+    adjusted_batch_metrics = (
+        counted_metrics and not fused_batch_metrics and mined_ok
+        and (self._num_hard_negatives is None or mined_hard_negatives))
     # multi-head queries: the fused max-sim kernels under the conditions of the 2-D fused route
     fused_multi_head = (
         q.dim() == 3 and self._loss is None and self._num_hard_negatives is None
         and q.shape[-1] <= 128 and 1 <= q.shape[1] <= MAX_FUSED_HEADS
-        and not (compute_batch_metrics and len(self._batch_metrics) > 0))
+        and not has_batch_metrics)
     need_matrix = ((q.dim() == 3 and not fused_multi_head) or self._loss is not None
-                   or (self._num_hard_negatives is not None and not fused_hard_negatives) or wide
-                   or (compute_batch_metrics and len(self._batch_metrics) > 0 and not fused_batch_metrics))
+                   or (self._num_hard_negatives is not None and not fused_hard_negatives
+                       and not mined_hard_negatives) or wide
+                   or (has_batch_metrics and not fused_batch_metrics and not adjusted_batch_metrics))
     scores = labels = None
     if need_matrix:
       scores, labels = self._logits_and_labels(
           q, c, candidate_sampling_probability, candidate_ids, score_mask)
 
+    accidental_ids = candidate_ids if self._remove_accidental_hits else None
+    tau = cut = None
     if self._loss is None and q.dim() == 2 and self._num_hard_negatives is None and not wide:
       loss = in_batch_softmax_loss(                                     # fused :172-210
-          q, c, sample_weight, self._temperature, candidate_sampling_probability,
-          candidate_ids if self._remove_accidental_hits else None, score_mask)
+          q, c, sample_weight, self._temperature, candidate_sampling_probability, accidental_ids, score_mask)
     elif fused_multi_head:
       loss = multi_head_in_batch_softmax_loss(                          # fused :172-176, :185-210
-          q, c, sample_weight, self._temperature, candidate_sampling_probability,
-          candidate_ids if self._remove_accidental_hits else None, score_mask)
+          q, c, sample_weight, self._temperature, candidate_sampling_probability, accidental_ids, score_mask)
     elif fused_hard_negatives:
       loss = hard_negative_softmax_loss(q, c, self._num_hard_negatives, sample_weight, self._temperature)
+    elif mined_hard_negatives:
+      loss, tau, cut = _mined_softmax(                                  # fused :178-210 with :205-208
+          q, c, self._num_hard_negatives, sample_weight, self._temperature, candidate_sampling_probability,
+          accidental_ids, score_mask)
     elif self._loss is None:
       # CategoricalCrossentropy(from_logits, SUM) on the explicit logits (:86-87, :210): row-wise HIP kernels
       loss = logits_softmax_ce_sum(scores, labels, sample_weight)
@@ -494,6 +630,9 @@ class Retrieval(torch.nn.Module, base.Task):
         for metric in self._batch_metrics:
           if fused_batch_metrics:
             metric.update_from_embeddings(q, c, sample_weight=sample_weight)
+          elif adjusted_batch_metrics:
+            metric.update_from_adjusted(q, c, sample_weight, self._temperature, candidate_sampling_probability,
+                                        accidental_ids, score_mask, tau, cut)
           else:
             metric.update_state(labels, scores.detach(), sample_weight=sample_weight)
 
