@@ -14,10 +14,13 @@
 //   G_bc  = gloss * w_b * (exp(S_bc - lse_b) - [b == c]) / T   where keep(b, c) and not masked, else 0
 //   count_b = #{c != b : keep(b, c) and S_bc > S_bb}
 //
-// Every kernel is the tile loop of softmax.hip: a wave owns 32 rows as the MFMA B operand and streams 32-row
-// tiles of the other side; a logit exists only in an accumulator register.  keep() compares RECOMPUTED logits
-// with tau for equality, so every kernel forms S_bc by the same tile_dot over the same fragments (the dc
-// kernel swaps the operand roles: each product commutes and the k order is the same) and the same mined_logit.
+// Every kernel instantiates a tile loop of softmax_shared.h with the mined policy (mined_logit, mined_keep, the
+// row's tau / cut): mined_scan_kernel is softmax_stream_queries with one consumer per mode -- the loss forward is
+// the shared OnlineSoftmax, the selection's and the count's consumers are below -- and mined_bwd_kernel is
+// softmax_bwd_body.  A wave owns 32 rows as the MFMA B operand and streams 32-row tiles of the other side; a logit
+// exists only in an accumulator register.  keep() compares RECOMPUTED logits with tau for equality, so every kernel
+// forms S_bc by the same tile_dot over the same fragments (the dc kernel swaps the operand roles: each product
+// commutes and the k order is the same) and the same mined_logit.
 //
 // Selection (exact, fixed launch sequence, no host read-back, no float atomics): a radix select over the
 // order-preserving uint32 image of S (f32_orderable), four 8-bit passes.  A pass re-scores the tiles; every
@@ -72,178 +75,168 @@ __device__ __forceinline__ bool mined_keep(float v, int64_t query, int64_t cand,
   return cand == query || v > tau || (v == tau && cand <= cut);
 }
 
-// Waves own 32 queries and stream the candidates of one split (softmax_fwd_kernel's loop); MODE selects what is done
-// with a tile of logits.  kModeHist runs with ONE wave per workgroup (its LDS histogram), the others with four.
-template <int DP, int MODE>
-__global__ void __launch_bounds__(256) mined_scan_kernel(const MinedArgs a) {
-  const SoftmaxArgs &s = a.s;
-  if (MODE == kModeFwd && blockIdx.x == 0 && threadIdx.x == 0) *s.ticket = 0u;  // re-arms the finalize kernel's ticket
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-  const int64_t nqb = (s.nq + 31) / 32;
-  if (wid >= nqb * s.nsplit) return;
-  const int64_t qb = wid / s.nsplit;
-  const int sp = (int)(wid - qb * s.nsplit);
-  const int j = lane & 31, h = lane >> 5;
-  const int64_t query = qb * 32 + j;
-  const bool qvalid = query < s.nq;
-  const bool vec_ok = (s.d == DP) && ((((uintptr_t)s.q) | ((uintptr_t)s.c)) % 16 == 0);
-
-  float tau_r = -__builtin_inff();
-  int64_t cut_r = kCutAll;
-  if (a.tau && qvalid) {
-    tau_r = a.tau[query];
-    cut_r = a.cut[query];
+// The policy (softmax_shared.h) of every kernel here; without tau every column is kept.
+struct MinedPolicy {
+  const MinedArgs &a;
+  struct Row {
+    float tau = -__builtin_inff();
+    int64_t cut = kCutAll;
+  };
+  __device__ __forceinline__ float logit(float dot, int64_t query, int64_t cand, float corr_c, int64_t id_q,
+                                         int64_t id_c, bool *masked) const {
+    return mined_logit(dot, query, cand, a, corr_c, id_q, id_c, masked);
   }
-  // the cut passes: leave when no row of the wave takes fewer ties than exist / has its r-th tie in this split
-  uint32_t want = 0, before = 0;
+  __device__ __forceinline__ Row row(int64_t query) const {
+    Row r;
+    if (a.tau) {
+      r.tau = a.tau[query];
+      r.cut = a.cut[query];
+    }
+    return r;
+  }
+  __device__ static __forceinline__ bool keep(float v, int64_t query, int64_t cand, Row r) {
+    return mined_keep(v, query, cand, r.tau, r.cut);
+  }
+};
+
+using MinedLane = QueryLane<MinedPolicy::Row>;
+
+// kModeHist (ONE wave per workgroup): every negative whose key matches the prefix fixed so far bumps its digit's bin
+// of the LDS histogram `lds` [32, kHistStride]; the non-zero bins are flushed into hist[nq, 256].
+struct HistConsumer {
+  const MinedArgs &a;
+  uint32_t *lds;
+  uint32_t prefix_r = 0;
+
+  template <class Frag>
+  __device__ __forceinline__ bool begin(const MinedLane &w, const Frag &) {
+    for (int i = w.lane; i < 32 * kHistStride; i += 64) lds[i] = 0u;
+    if (w.qvalid) prefix_r = a.prefix[w.query];
+    __syncthreads();  // one wave per workgroup
+    return true;
+  }
+  __device__ __forceinline__ void element(const MinedLane &w, int, int64_t cand, bool valid, float v) {
+    const int shift = 24 - 8 * a.pass;
+    const uint32_t key = f32_orderable(v);
+    if (valid && cand != w.query && (((key ^ prefix_r) >> shift) >> 8) == 0u)
+      atomicAdd(&lds[w.j * kHistStride + ((key >> shift) & 255u)], 1u);
+  }
+  __device__ __forceinline__ void tile_end(const MinedLane &, int64_t) {}
+  __device__ __forceinline__ void finish(const MinedLane &w) {
+    __syncthreads();
+    for (int i = w.lane; i < 32 * 256; i += 64) {
+      const int row = i >> 8, bin = i & 255;
+      const uint32_t v = lds[row * kHistStride + bin];
+      if (v != 0u && w.qb * 32 + row < a.s.nq) atomicAdd(&a.hist[(w.qb * 32 + row) * 256 + bin], v);
+    }
+  }
+};
+
+// The cut passes.  kModeTieCount: ties with tau per (split, row); kModeTieFind: the column of the r-th tie of a row,
+// in the split that holds it.  The wave leaves when no row of it takes fewer ties than exist / has its r-th tie here.
+template <bool FIND>
+struct TieConsumer {
+  const MinedArgs &a;
+  uint32_t want = 0, running = 0, tiebits = 0;
   bool active = false;
-  if constexpr (MODE == kModeTieCount || MODE == kModeTieFind) {
-    active = qvalid && a.need[query] != 0u;
-    if constexpr (MODE == kModeTieFind) {
+  int64_t found = -1;
+
+  template <class Frag>
+  __device__ __forceinline__ bool begin(const MinedLane &w, const Frag &) {
+    active = w.qvalid && a.need[w.query] != 0u;
+    if constexpr (FIND) {
       if (active) {
-        want = a.krem[query];
-        for (int p = 0; p < sp; ++p) before += a.tiecnt[(int64_t)p * s.nq + query];
-        const uint32_t mine = a.tiecnt[(int64_t)sp * s.nq + query];
-        active = before < want && want <= before + mine;
+        want = a.krem[w.query];
+        for (int p = 0; p < w.sp; ++p) running += a.tiecnt[(int64_t)p * a.s.nq + w.query];
+        const uint32_t mine = a.tiecnt[(int64_t)w.sp * a.s.nq + w.query];
+        active = running < want && want <= running + mine;
       }
     }
-    if (!__any(active)) return;
+    return __any(active);
   }
-
-  __shared__ uint32_t hist_lds[MODE == kModeHist ? 32 * kHistStride : 1];
-  uint32_t prefix_r = 0;
-  if constexpr (MODE == kModeHist) {
-    for (int i = lane; i < 32 * kHistStride; i += 64) hist_lds[i] = 0u;
-    if (qvalid) prefix_r = a.prefix[query];
-    __syncthreads();  // one wave per workgroup
+  __device__ __forceinline__ void element(const MinedLane &w, int r, int64_t cand, bool valid, float v) {
+    if (valid && cand != w.query && v == w.row.tau) tiebits |= 1u << tile_row_of_reg(r, w.h);
   }
-  const int shift = 24 - 8 * a.pass;
+  __device__ __forceinline__ void tile_end(const MinedLane &, int64_t c0) {
+    // a query's 32 candidates of the tile sit in its two lane halves: bit t of `full` = tile row t ties with tau
+    const uint32_t full = tiebits | (uint32_t)__shfl_xor((int)tiebits, 32);
+    const uint32_t pc = (uint32_t)__popc(full);
+    if constexpr (FIND) {
+      if (active && found < 0 && running + pc >= want) {
+        uint32_t bits = full;
+        for (uint32_t skip = want - running - 1u; skip > 0u; --skip) bits &= bits - 1u;
+        found = c0 + (__ffs((int)bits) - 1);
+      }
+    }
+    running += pc;
+    tiebits = 0;
+  }
+  __device__ __forceinline__ void finish(const MinedLane &w) {
+    if constexpr (FIND) {
+      if (w.h == 0 && active && found >= 0) a.cut_w[w.query] = found;
+    } else {
+      if (w.h == 0 && w.qvalid) a.tiecnt[(int64_t)w.sp * a.s.nq + w.query] = running;
+    }
+  }
+};
 
-  float bq[DP / 2];
-  load_row_frag<DP>(bq, s.q, query, qvalid, s.d, h, vec_ok);
-  const int64_t id_q = (s.ids && qvalid) ? s.ids[query] : 0;
-
-  // kModeCount: the positive logit from the diagonal tile (this wave's queries against candidates qb*32 .. +31), by
-  // the arithmetic of every other tile: it ties exactly with copies of itself
+// kModeCount: the kept negatives strictly above the positive, per (split, row); split 0 also writes the positive.
+struct CountConsumer {
+  const MinedArgs &a;
   float pos = 0.0f;
-  if constexpr (MODE == kModeCount) {
-    float ad[DP / 2];
-    load_row_frag<DP>(ad, s.c, query, qvalid, s.d, h, vec_ok);  // nq <= nc: a valid query is a valid candidate row
-    const f32x16 acc = tile_dot<DP>(ad, bq);
+  uint32_t count = 0;
+
+  // the positive logit from the diagonal tile (this wave's queries against candidates qb*32 .. +31), by the
+  // arithmetic of every other tile: it ties exactly with copies of itself
+  template <int HALF>
+  __device__ __forceinline__ bool begin(const MinedLane &w, const float (&bq)[HALF]) {
+    const SoftmaxArgs &s = a.s;
+    const bool vec_ok = (s.d == 2 * HALF) && ((((uintptr_t)s.q) | ((uintptr_t)s.c)) % 16 == 0);
+    float ad[HALF];
+    load_row_frag<2 * HALF>(ad, s.c, w.query, w.qvalid, s.d, w.h, vec_ok);  // nq <= nc: a query is a candidate row
+    const f32x16 acc = tile_dot<2 * HALF>(ad, bq);
     float own = 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (tile_row_of_reg(r, h) == j && qvalid) {
+      if (tile_row_of_reg(r, w.h) == w.j && w.qvalid) {
         bool masked;
-        own = mined_logit(acc[r], query, query, a, s.corr ? s.corr[query] : 0.0f, id_q, id_q, &masked);
+        own = mined_logit(acc[r], w.query, w.query, a, s.corr ? s.corr[w.query] : 0.0f, w.id_q, w.id_q, &masked);
       }
     const float other = __shfl_xor(own, 32);
-    pos = (((j >> 2) & 1) == h) ? own : other;  // tile row j lives in lane half (j >> 2) & 1
+    pos = (((w.j >> 2) & 1) == w.h) ? own : other;  // tile row j lives in lane half (j >> 2) & 1
+    return true;
   }
-
-  float m = -__builtin_inff(), l = 0.0f, fpos = 0.0f;
-  bool haspos = false;
-  uint32_t count = 0, running = before;
-  int64_t found = -1;
-  const int64_t c_lo = (int64_t)sp * s.split_len;
-  int64_t c_hi = c_lo + s.split_len;
-  if (c_hi > s.nc) c_hi = s.nc;
-
-  float af_next[DP / 2];
-  load_row_frag<DP>(af_next, s.c, c_lo + j, c_lo + j < s.nc && c_lo < c_hi, s.d, h, vec_ok);
-  for (int64_t c0 = c_lo; c0 < c_hi; c0 += 32) {
-    float af[DP / 2];
-#pragma unroll
-    for (int k = 0; k < DP / 2; ++k) af[k] = af_next[k];
-    if (c0 + 32 < c_hi) load_row_frag<DP>(af_next, s.c, c0 + 32 + j, c0 + 32 + j < s.nc, s.d, h, vec_ok);
-    const f32x16 acc = tile_dot<DP>(af, bq);
-
-    float sv[16];
-    float tmax = -__builtin_inff();
-    uint32_t tiebits = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int trow = tile_row_of_reg(r, h);
-      const int64_t cand = c0 + trow;
-      float kept = -__builtin_inff();
-      if (qvalid && cand < c_hi) {
-        bool masked;
-        const float v = mined_logit(acc[r], query, cand, a, s.corr ? s.corr[cand] : 0.0f, id_q,
-                                    s.ids ? s.ids[cand] : 0, &masked);
-        if constexpr (MODE == kModeHist) {
-          const uint32_t key = f32_orderable(v);
-          if (cand != query && (((key ^ prefix_r) >> shift) >> 8) == 0u)
-            atomicAdd(&hist_lds[j * kHistStride + ((key >> shift) & 255u)], 1u);
-        } else if constexpr (MODE == kModeTieCount || MODE == kModeTieFind) {
-          if (cand != query && v == tau_r) tiebits |= 1u << trow;
-        } else if constexpr (MODE == kModeCount) {
-          if (cand != query && mined_keep(v, query, cand, tau_r, cut_r) && v > pos) ++count;
-        } else {
-          if (mined_keep(v, query, cand, tau_r, cut_r)) kept = v;
-          if (cand == query) {
-            fpos = v;
-            haspos = true;
-          }
-        }
-      }
-      sv[r] = kept;
-      tmax = fmaxf(tmax, kept);
-    }
-    if constexpr (MODE == kModeFwd) {
-      if (tmax > m) {
-        l *= __expf(m - tmax);
-        m = tmax;
-      }
-      if (m > -__builtin_inff()) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) l += __expf(sv[r] - m);
-      }
-    }
-    if constexpr (MODE == kModeTieCount || MODE == kModeTieFind) {
-      // a query's 32 candidates of the tile sit in its two lane halves: bit t of `full` = tile row t ties with tau
-      const uint32_t full = tiebits | (uint32_t)__shfl_xor((int)tiebits, 32);
-      const uint32_t pc = (uint32_t)__popc(full);
-      if constexpr (MODE == kModeTieFind) {
-        if (active && found < 0 && running + pc >= want) {
-          uint32_t bits = full;
-          for (uint32_t skip = want - running - 1u; skip > 0u; --skip) bits &= bits - 1u;
-          found = c0 + (__ffs((int)bits) - 1);
-        }
-      }
-      running += pc;
-    }
+  __device__ __forceinline__ void element(const MinedLane &w, int, int64_t cand, bool valid, float v) {
+    if (valid && cand != w.query && MinedPolicy::keep(v, w.query, cand, w.row) && v > pos) ++count;
   }
-
-  if constexpr (MODE == kModeHist) {
-    __syncthreads();
-    for (int i = lane; i < 32 * 256; i += 64) {
-      const int row = i >> 8, bin = i & 255;
-      const uint32_t v = hist_lds[row * kHistStride + bin];
-      if (v != 0u && qb * 32 + row < s.nq) atomicAdd(&a.hist[(qb * 32 + row) * 256 + bin], v);
-    }
-  } else if constexpr (MODE == kModeTieCount) {
-    if (h == 0 && qvalid) a.tiecnt[(int64_t)sp * s.nq + query] = running;
-  } else if constexpr (MODE == kModeTieFind) {
-    if (h == 0 && active && found >= 0) a.cut_w[query] = found;
-  } else if constexpr (MODE == kModeCount) {
+  __device__ __forceinline__ void tile_end(const MinedLane &, int64_t) {}
+  __device__ __forceinline__ void finish(const MinedLane &w) {
     const uint32_t total = count + (uint32_t)__shfl_xor((int)count, 32);
-    if (h == 0 && qvalid) {
-      a.cnt_part[(int64_t)sp * s.nq + query] = total;
-      if (sp == 0) s.ppos[query] = pos;
+    if (w.h == 0 && w.qvalid) {
+      a.cnt_part[(int64_t)w.sp * a.s.nq + w.query] = total;
+      if (w.sp == 0) a.s.ppos[w.query] = pos;
     }
+  }
+};
+
+// Waves own 32 queries and stream the candidates of one split; MODE selects the consumer of a tile of logits.
+// kModeHist runs with ONE wave per workgroup (its LDS histogram), the others with four.
+template <int DP, int MODE>
+__global__ void __launch_bounds__(256) mined_scan_kernel(const MinedArgs a) {
+  const MinedPolicy pol{a};
+  if constexpr (MODE == kModeHist) {
+    __shared__ uint32_t hist_lds[32 * kHistStride];
+    HistConsumer con{a, hist_lds};
+    softmax_stream_queries<DP, false, 1>(a.s, pol, con);
+  } else if constexpr (MODE == kModeFwd) {
+    OnlineSoftmax<MinedPolicy> con;
+    softmax_stream_queries<DP, false, 4>(a.s, pol, con);
+  } else if constexpr (MODE == kModeCount) {
+    CountConsumer con{a};
+    softmax_stream_queries<DP, false, 4>(a.s, pol, con);
   } else {
-    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32);
-    const float mm = fmaxf(m, m2);
-    float ll = 0.0f;
-    if (m > -__builtin_inff()) ll += l * __expf(m - mm);
-    if (m2 > -__builtin_inff()) ll += l2 * __expf(m2 - mm);
-    if (h == 0 && qvalid) {
-      s.pm[(int64_t)sp * s.nq + query] = mm;
-      s.pl[(int64_t)sp * s.nq + query] = ll;
-    }
-    if (haspos) s.ppos[query] = fpos;
+    TieConsumer<MODE == kModeTieFind> con{a};
+    softmax_stream_queries<DP, false, 4>(a.s, pol, con);
   }
 }
 
@@ -309,131 +302,10 @@ __global__ void __launch_bounds__(256) mined_count_reduce_kernel(const MinedArgs
 }
 
 // softmax_bwd_kernel of the 2-D route with keep() applied to every recomputed logit.
-// ROWS_ARE_QUERIES = true : wave owns 32 queries, streams candidates, partial dq.
-// ROWS_ARE_QUERIES = false: wave owns 32 candidates, streams queries, partial dc.
 template <int DP, bool ROWS_ARE_QUERIES>
 __global__ void __launch_bounds__(256) mined_bwd_kernel(const MinedArgs a) {
-  const SoftmaxArgs &s = a.s;
-  constexpr int NFB = (DP + 31) / 32;  // 32-feature output blocks
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t nrb = ROWS_ARE_QUERIES ? (s.nq + 31) / 32 : (s.nc + 31) / 32;
-  const int64_t n_s = ROWS_ARE_QUERIES ? s.nc : s.nq;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-  if (wid >= nrb * s.nsplit) return;
-  const int64_t rb = wid / s.nsplit;
-  const int sp = (int)(wid - rb * s.nsplit);
-  const int j = lane & 31, h = lane >> 5;
-  const bool vec_ok = (s.d == DP) && ((((uintptr_t)s.q) | ((uintptr_t)s.c)) % 16 == 0);
-
-  const int64_t rrow = rb * 32 + j;  // the owned row of q / of c, and of the output
-  const bool rvalid = ROWS_ARE_QUERIES ? rrow < s.nq : rrow < s.nc;
-
-  float br[DP / 2];
-  load_row_frag<DP>(br, ROWS_ARE_QUERIES ? s.q : s.c, rrow, rvalid, s.d, h, vec_ok);
-
-  // per-lane constants of the owned row
-  float lse_r = 0.0f, w_r = 1.0f, corr_r = 0.0f, tau_r = -__builtin_inff();
-  int64_t id_r = 0, cut_r = kCutAll;
-  if (rvalid) {
-    if (ROWS_ARE_QUERIES) {
-      lse_r = s.lse[rrow];
-      if (s.w) w_r = s.w[rrow];
-      if (s.ids) id_r = s.ids[rrow];  // nq <= nc, so a query is also a valid candidate row
-      if (a.tau) {
-        tau_r = a.tau[rrow];
-        cut_r = a.cut[rrow];
-      }
-    } else {
-      if (s.corr) corr_r = s.corr[rrow];
-      if (s.ids) id_r = s.ids[rrow];
-    }
-  }
-  const float gl = (s.gloss ? *s.gloss : 1.0f) * s.inv_t;
-
-  f32x16 outacc[NFB];
-#pragma unroll
-  for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) outacc[fb][r] = 0.0f;
-
-  const int64_t s_lo = (int64_t)sp * s.split_len;
-  int64_t s_hi = s_lo + s.split_len;
-  if (s_hi > n_s) s_hi = n_s;
-  const float *sdata = ROWS_ARE_QUERIES ? s.c : s.q;
-
-  // the streamed tile: one tile ahead in registers (the first GEMM's A fragment), mirrored into this wave's LDS
-  // slab so that the second GEMM reads it transposed (lane = feature)
-  constexpr int kLd = DP + 4;  // floats per LDS row (+16 B: rows start in different bank groups)
   extern __shared__ __attribute__((aligned(16))) float smem_mined[];
-  float *slab = smem_mined + (size_t)wave * 32 * kLd;
-  float af_next[DP / 2];
-  load_row_frag<DP>(af_next, sdata, s_lo + j, s_lo + j < n_s && s_lo < s_hi, s.d, h, vec_ok);
-
-  for (int64_t s0 = s_lo; s0 < s_hi; s0 += 32) {
-    float af[DP / 2];
-#pragma unroll
-    for (int k = 0; k < DP / 2; ++k) af[k] = af_next[k];
-    if (s0 + 32 < s_hi) load_row_frag<DP>(af_next, sdata, s0 + 32 + j, s0 + 32 + j < n_s, s.d, h, vec_ok);
-#pragma unroll
-    for (int m4 = 0; m4 < DP / 8; ++m4)
-      *reinterpret_cast<float4 *>(slab + j * kLd + h * (DP / 2) + 4 * m4) =
-          make_float4(af[4 * m4], af[4 * m4 + 1], af[4 * m4 + 2], af[4 * m4 + 3]);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x16 acc = tile_dot<DP>(af, br);
-
-    float g[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float gg = 0.0f;
-      const int64_t srow = s0 + tile_row_of_reg(r, h);
-      if (rvalid && srow < s_hi) {
-        const int64_t query = ROWS_ARE_QUERIES ? rrow : srow;
-        const int64_t cand = ROWS_ARE_QUERIES ? srow : rrow;
-        const float corr_c = ROWS_ARE_QUERIES ? (s.corr ? s.corr[cand] : 0.0f) : corr_r;
-        const int64_t id_q = ROWS_ARE_QUERIES ? id_r : (s.ids ? s.ids[query] : 0);
-        const int64_t id_c = ROWS_ARE_QUERIES ? (s.ids ? s.ids[cand] : 0) : id_r;
-        bool masked;
-        const float v = mined_logit(acc[r], query, cand, a, corr_c, id_q, id_c, &masked);
-        const float tau_q = ROWS_ARE_QUERIES ? tau_r : (a.tau ? a.tau[query] : -__builtin_inff());
-        const int64_t cut_q = ROWS_ARE_QUERIES ? cut_r : (a.tau ? a.cut[query] : kCutAll);
-        if (!masked && mined_keep(v, query, cand, tau_q, cut_q)) {
-          const float lse_q = ROWS_ARE_QUERIES ? lse_r : s.lse[query];
-          const float w_q = ROWS_ARE_QUERIES ? w_r : (s.w ? s.w[query] : 1.0f);
-          gg = w_q * (__expf(v - lse_q) - (cand == query ? 1.0f : 0.0f)) * gl;
-        }
-      }
-      g[r] = gg;
-    }
-
-    // out^T[feature][owned row] += sum over the 32 streamed rows of X[srow][feature] * G[srow][row]: MFMA step r
-    // contracts the streamed-row pair (tile_row_of_reg(r, 0), tile_row_of_reg(r, 1)), where g[r] lives
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float *xrow = slab + tile_row_of_reg(r, h) * kLd;
-#pragma unroll
-      for (int fb = 0; fb < NFB; ++fb) {
-        const int feat = fb * 32 + j;
-        const float av = (feat < DP) ? xrow[feat] : 0.0f;
-        outacc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, g[r], outacc[fb], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();  // the slab is rewritten by the next tile
-  }
-
-  if (rvalid) {
-    const int64_t n_out = ROWS_ARE_QUERIES ? s.nq : s.nc;
-    float *dst = s.partial + ((int64_t)sp * n_out + rrow) * s.d;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int feat = fb * 32 + tile_row_of_reg(r, h);
-        if (feat < s.d) dst[feat] = outacc[fb][r];
-      }
-  }
+  softmax_bwd_body<DP, ROWS_ARE_QUERIES, false>(a.s, MinedPolicy{a}, smem_mined);
 }
 
 template <int DP, int MODE>
@@ -457,34 +329,23 @@ static void launch_mined_bwd(const MinedArgs &a, hipStream_t st) {
   hipLaunchKernelGGL((mined_bwd_kernel<DP, RQ>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, a);
 }
 
-// One workspace serves the four calls (each uses it from the start): the selection's bins and per-row state,
-// the forward's partials, the backward's two partial-gradient buffers, the count's partials.
-struct MinedLayout {
-  int nsq, nsc;
-  int64_t lenq, lenc;
-  size_t select, fwd, bwd, count;
-  size_t bytes() const { return std::max(std::max(select, fwd), std::max(bwd, count)); }
-};
-
-static MinedLayout mined_layout(int64_t nq, int64_t nc, int d) {
-  MinedLayout L;
-  const int64_t target = resolve_target_waves();
-  plan_queries(target, nq, 0, nc, &L.nsq, &L.lenq);
-  plan_candidates(target, nq, 0, nc, &L.nsc, &L.lenc);
-  L.select = al((size_t)nq * 256 * 4) + 3 * al((size_t)nq * 4) + al((size_t)L.nsq * nq * 4);
-  L.fwd = 2 * al((size_t)L.nsq * nq * 4) + al((size_t)nq * 4) + al((size_t)((nq + 255) / 256) * 8) + al(4);
-  L.bwd = al((size_t)L.nsq * nq * d * 4) + al((size_t)L.nsc * nc * d * 4);
-  L.count = al((size_t)L.nsq * nq * 4) + al((size_t)nq * 4);
-  return L;
+// One workspace serves the four calls (each uses it from the start): the selection's bins and per-row state, the
+// count's partials, and the loss kernels' SoftmaxLayout (softmax_shared.h) at one head.
+static size_t mined_bytes(int64_t nq, int64_t nc, int d) {
+  const SoftmaxLayout L = softmax_layout(nq, 1, nc, d);
+  const size_t select = al((size_t)nq * 256 * 4) + 3 * al((size_t)nq * 4) + al((size_t)L.nsq * nq * 4);
+  const size_t count = al((size_t)L.nsq * nq * 4) + al((size_t)nq * 4);
+  return std::max(std::max(select, L.fwd), std::max(L.bwd, count));
 }
 
+// s.inv_t = 1 / t; the query plan (the scans' and the dq kernel's) is set, the loss runners set their own
 static MinedArgs mined_args(const float *q, const float *c, int64_t nq, int64_t nc, int d, const float *w, float t,
                             const float *corr, const int64_t *ids, const uint8_t *mask, const float *tau,
                             const int64_t *cut) {
   MinedArgs a = {};
-  a.s.q = q; a.s.c = c; a.s.nq = nq; a.s.nc = nc; a.s.d = d;
-  a.s.w = w; a.s.inv_t = 1.0f / t; a.s.corr = corr; a.s.ids = ids; a.s.mask = mask;
-  a.s.heads = 1; a.s.lhp = 0;
+  a.s = softmax_args(q, c, nq, 1, nc, d, w, 1.0f / t, corr, ids, mask);
+  const SoftmaxLayout L = softmax_layout(nq, 1, nc, d);
+  a.s.nsplit = L.nsq; a.s.split_len = L.lenq;
   a.t = t; a.tau = tau; a.cut = cut;
   return a;
 }
@@ -504,18 +365,18 @@ static int mined_check(const float *q, const float *c, int64_t nq, int64_t nc, i
   TFRS_CHECK_ARG((tau == nullptr) == (cut == nullptr), "%s: tau and cut come together (both NULL: keep everything)",
                  who);
   TFRS_CHECK_ARG(ws, "%s: NULL workspace", who);
-  TFRS_CHECK_ARG(ws_bytes >= mined_layout(nq, nc, d).bytes(), "%s: workspace too small", who);
+  TFRS_CHECK_ARG(ws_bytes >= mined_bytes(nq, nc, d), "%s: workspace too small", who);
   return TFRS_OK;
 }
 
 extern "C" size_t tfrs_inbatch_mined_workspace_bytes(int64_t nq, int64_t nc, int d) {
   if (nq < 1 || nc < nq || d < 1 || d > TFRS_MAX_DIM) return 256;
-  return mined_layout(nq, nc, d).bytes();
+  return mined_bytes(nq, nc, d);
 }
 
 extern "C" int tfrs_inbatch_mined_plan(int64_t nq, int64_t nc, int64_t *out) {
   TFRS_CHECK_ARG(nq >= 1 && nc >= nq && out, "inbatch_mined_plan: bad argument");
-  const MinedLayout L = mined_layout(nq, nc, 1);
+  const SoftmaxLayout L = softmax_layout(nq, 1, nc, 1);
   out[0] = L.nsq; out[1] = L.lenq; out[2] = L.nsc; out[3] = L.lenc;
   return TFRS_OK;
 }
@@ -533,8 +394,6 @@ extern "C" int tfrs_inbatch_mined_select(const float *q, const float *c, int64_t
   hipStream_t st = (hipStream_t)stream;
   MinedArgs a = mined_args(q, c, nq, nc, d, nullptr, temperature, log_q_correction, cand_ids, score_mask, nullptr,
                            nullptr);
-  const MinedLayout L = mined_layout(nq, nc, d);
-  a.s.nsplit = L.nsq; a.s.split_len = L.lenq;
   char *p = static_cast<char *>(workspace);
   a.hist = reinterpret_cast<uint32_t *>(p); p += al((size_t)nq * 256 * 4);
   a.prefix = reinterpret_cast<uint32_t *>(p); p += al((size_t)nq * 4);
@@ -576,19 +435,7 @@ extern "C" int tfrs_inbatch_mined_ce_fwd(const float *q, const float *c, int64_t
   hipStream_t st = (hipStream_t)stream;
   MinedArgs a = mined_args(q, c, nq, nc, d, sample_weight, temperature, log_q_correction, cand_ids, score_mask, tau,
                            cut);
-  const MinedLayout L = mined_layout(nq, nc, d);
-  a.s.nsplit = L.nsq; a.s.split_len = L.lenq;
-  char *p = static_cast<char *>(workspace);
-  a.s.pm = reinterpret_cast<float *>(p); p += al((size_t)L.nsq * nq * 4);
-  a.s.pl = reinterpret_cast<float *>(p); p += al((size_t)L.nsq * nq * 4);
-  a.s.ppos = reinterpret_cast<float *>(p); p += al((size_t)nq * 4);
-  double *block_part = reinterpret_cast<double *>(p); p += al((size_t)((nq + 255) / 256) * 8);
-  a.s.ticket = reinterpret_cast<uint32_t *>(p);
-  scan<kModeFwd>(a, st);
-  TFRS_LAUNCH_CHECK();
-  softmax_launch_finalize(a.s, out_loss, out_lse, out_pos, block_part, st);
-  TFRS_LAUNCH_CHECK();
-  return TFRS_OK;
+  return softmax_run_fwd(a.s, out_loss, out_lse, out_pos, workspace, st, [&](auto) { scan<kModeFwd>(a, st); });
 }
 
 extern "C" int tfrs_inbatch_mined_ce_bwd(const float *q, const float *c, int64_t nq, int64_t nc, int d,
@@ -605,24 +452,9 @@ extern "C" int tfrs_inbatch_mined_ce_bwd(const float *q, const float *c, int64_t
   MinedArgs a = mined_args(q, c, nq, nc, d, sample_weight, temperature, log_q_correction, cand_ids, score_mask, tau,
                            cut);
   a.s.lse = lse; a.s.gloss = gloss;
-  const MinedLayout L = mined_layout(nq, nc, d);
-  char *p = static_cast<char *>(workspace);
-  // dq: waves own query blocks, stream candidates
-  a.s.nsplit = L.nsq; a.s.split_len = L.lenq;
-  a.s.partial = reinterpret_cast<float *>(p);
-  for_padded_dim(d, [&](auto dp) { launch_mined_bwd<decltype(dp)::value, true>(a, st); });
-  TFRS_LAUNCH_CHECK();
-  softmax_launch_reduce(a.s.partial, a.s.nsplit, nq * d, dq, st);
-  TFRS_LAUNCH_CHECK();
-  // dc: waves own candidates, stream queries
-  p += al((size_t)L.nsq * nq * d * 4);
-  a.s.nsplit = L.nsc; a.s.split_len = L.lenc;
-  a.s.partial = reinterpret_cast<float *>(p);
-  for_padded_dim(d, [&](auto dp) { launch_mined_bwd<decltype(dp)::value, false>(a, st); });
-  TFRS_LAUNCH_CHECK();
-  softmax_launch_reduce(a.s.partial, a.s.nsplit, nc * d, dc, st);
-  TFRS_LAUNCH_CHECK();
-  return TFRS_OK;
+  return softmax_run_bwd(a.s, dq, dc, workspace, st, [&](auto dp, auto rq) {
+    launch_mined_bwd<decltype(dp)::value, decltype(rq)::value>(a, st);
+  });
 }
 
 extern "C" int tfrs_inbatch_mined_rank_count(const float *q, const float *c, int64_t nq, int64_t nc, int d,
@@ -636,10 +468,8 @@ extern "C" int tfrs_inbatch_mined_rank_count(const float *q, const float *c, int
   if (rc != TFRS_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   MinedArgs a = mined_args(q, c, nq, nc, d, nullptr, temperature, log_q_correction, cand_ids, score_mask, tau, cut);
-  const MinedLayout L = mined_layout(nq, nc, d);
-  a.s.nsplit = L.nsq; a.s.split_len = L.lenq;
   char *p = static_cast<char *>(workspace);
-  a.cnt_part = reinterpret_cast<uint32_t *>(p); p += al((size_t)L.nsq * nq * 4);
+  a.cnt_part = reinterpret_cast<uint32_t *>(p); p += al((size_t)a.s.nsplit * nq * 4);
   a.s.ppos = reinterpret_cast<float *>(p);
   scan<kModeCount>(a, st);
   TFRS_LAUNCH_CHECK();

@@ -24,8 +24,15 @@ combined with hard negatives, batch metrics or more than 32 heads -- computes it
 GEMM and then follows the reference's op sequence on that tensor.  ``TFRS_RETRIEVAL_EXPLICIT=1`` (read per call) sends
 hard negatives / batch metrics over adjusted logits back to that route: the comparator of tests and
 ``tools/bench_hard_negatives.py``.
+
+All of the above is ONE decision, taken by the pure function ``pick_routes`` from the facts of a call's configuration:
+a ``LossRoute`` (fused 2-D, fused multi-head, top-K hard negatives, mined, matrix cross-entropy, custom loss) and a
+``MetricRoute`` (none, rank count on plain dot products, rank count on adjusted logits, matrix).
+``Retrieval.forward`` dispatches on the two values and builds the matrix exactly when one of them uses it
+(``needs_matrix``); ``tests/test_retrieval_route_host.py`` enumerates the function on the host.
 """
 
+import enum
 import os
 from typing import Callable, List, Optional, Sequence, Union
 
@@ -341,22 +348,15 @@ class TopKCategoricalAccuracy:
     positive's, so the batch's candidates are swept by the rank-count kernel
     (``tfrs_rank_count_accumulate``: f32 MFMA, the d-ordered fma chain -- the positive ties exactly
     with its own column) and ``tfrs_topk_hits_update`` turns the counts into hit indicators."""
-    import ctypes
     lib = _lib.load()
     nq, d = q.shape
     q = q.detach().to(torch.float32).contiguous()
     c = c.detach().to(torch.float32).contiguous()
     counts = torch.zeros((nq,), dtype=torch.int32, device=q.device)
-    hits = torch.empty((1, nq), dtype=torch.float32, device=q.device)
-    scratch = torch.zeros((3,), dtype=torch.float32, device=q.device)     # state[2], result[1] (unused)
-    stream = _lib.current_stream()
     _lib.check(lib.tfrs_rank_count_accumulate(
         _lib.ptr(q), _lib.ptr(c), nq, d, _lib.ptr(c), None, 0, c.shape[0], c.shape[0], _lib.ptr(counts), 1,
-        stream))
-    ks = (ctypes.c_int32 * 1)(int(self.k))
-    _lib.check(lib.tfrs_topk_hits_update(_lib.ptr(counts), nq, ks, 1, None, _lib.ptr(scratch),
-                                         _lib.ptr(scratch[2:]), _lib.ptr(hits), stream))
-    self._mean.update_state(hits[0], sample_weight)
+        _lib.current_stream()))
+    self._update_from_counts(counts, sample_weight)
 
   def update_from_adjusted(self, q: torch.Tensor, c: torch.Tensor, sample_weight=None, temperature=None,
                            candidate_sampling_probability=None, candidate_ids=None, score_mask=None,
@@ -365,24 +365,29 @@ class TopKCategoricalAccuracy:
     ``tfrs_inbatch_mined_rank_count`` re-scores the batch with the temperature division, the sampling correction,
     accidental-hit removal and the score mask applied in registers and counts, per row, the kept negatives strictly
     above the positive.  ``tau`` / ``cut``: the kept set of the mined loss (``None``: every column is kept)."""
-    import ctypes
     lib = _lib.load()
     nq, d = q.shape
     q = q.detach().to(torch.float32).contiguous()
     c = c.detach().to(torch.float32).contiguous()
     _, corr, ids, mask = _logit_options(q.device, None, candidate_sampling_probability, candidate_ids, score_mask)
     counts = torch.empty((nq,), dtype=torch.int32, device=q.device)
-    hits = torch.empty((1, nq), dtype=torch.float32, device=q.device)
-    scratch = torch.zeros((3,), dtype=torch.float32, device=q.device)     # state[2], result[1] (unused)
     ws = _MinedSoftmaxFn._workspace(lib, q, c)
-    stream = _lib.current_stream()
     _lib.check(lib.tfrs_inbatch_mined_rank_count(
         _lib.ptr(q), _lib.ptr(c), nq, c.shape[0], d, 1.0 if temperature is None else float(temperature),
         _lib.ptr(corr), _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(tau), _lib.ptr(cut), _lib.ptr(counts), _lib.ptr(ws),
-        ws.numel(), stream))
+        ws.numel(), _lib.current_stream()))
+    self._update_from_counts(counts, sample_weight)
+
+  def _update_from_counts(self, counts: torch.Tensor, sample_weight) -> None:
+    """The tail of both matrix-free updates: per-row rank counts (bit 31: a non-finite positive) become hit
+    indicators (``tfrs_topk_hits_update``) and enter the weighted mean."""
+    import ctypes
+    nq = counts.shape[0]
+    hits = torch.empty((1, nq), dtype=torch.float32, device=counts.device)
+    scratch = torch.zeros((3,), dtype=torch.float32, device=counts.device)     # state[2], result[1] (unused)
     ks = (ctypes.c_int32 * 1)(int(self.k))
-    _lib.check(lib.tfrs_topk_hits_update(_lib.ptr(counts), nq, ks, 1, None, _lib.ptr(scratch),
-                                         _lib.ptr(scratch[2:]), _lib.ptr(hits), stream))
+    _lib.check(_lib.load().tfrs_topk_hits_update(_lib.ptr(counts), nq, ks, 1, None, _lib.ptr(scratch),
+                                                 _lib.ptr(scratch[2:]), _lib.ptr(hits), _lib.current_stream()))
     self._mean.update_state(hits[0], sample_weight)
 
   def result(self):
@@ -435,6 +440,73 @@ class _LogitsCeFn(torch.autograd.Function):
 def logits_softmax_ce_sum(scores: torch.Tensor, labels: torch.Tensor,
                           sample_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
   return _LogitsCeFn.apply(scores, labels, sample_weight)
+
+
+class LossRoute(enum.Enum):
+  """How ``Retrieval.forward`` computes the loss."""
+  FUSED_2D = "fused 2-D"                        # in_batch_softmax_loss
+  FUSED_MULTI_HEAD = "fused multi-head"         # multi_head_in_batch_softmax_loss
+  TOPK_HARD_NEGATIVES = "top-K hard negatives"  # hard_negative_softmax_loss: plain dot products, the top-K search
+  MINED = "mined"                               # mined_in_batch_softmax_loss: radix select + keep predicate
+  MATRIX_CE = "matrix cross-entropy"            # the built-in loss on the explicit [B, C] logits
+  CUSTOM = "custom loss"                        # a user-supplied loss: its contract IS the matrix
+
+
+class MetricRoute(enum.Enum):
+  """How ``Retrieval.forward`` updates ``batch_metrics``."""
+  NONE = "none"
+  PLAIN_COUNT = "rank count on plain dot products"    # TopKCategoricalAccuracy.update_from_embeddings
+  ADJUSTED_COUNT = "rank count on adjusted logits"    # ... .update_from_adjusted (the mined kept set included)
+  MATRIX = "matrix"                                   # update_state on the explicit [B, C] logits
+
+
+def pick_routes(*, custom_loss: bool, query_rank: int, dim: int, heads: int, nq: int, nc: int,
+                num_hard_negatives: Optional[int], temperature: bool, sampling_correction: bool,
+                accidental_hits: bool, score_mask: bool, batch_metric_classes: Sequence[type], explicit: bool):
+  """``(LossRoute, MetricRoute)`` of one ``Retrieval.forward`` call, from the facts of its configuration alone:
+  whether a user loss is set, the queries' rank / embedding dim / heads (rank 3), the row counts,
+  ``num_hard_negatives``, which logit options are set, the classes of the batch metrics that will be updated (empty: none) and the
+  ``TFRS_RETRIEVAL_EXPLICIT=1`` switch.  The explicit ``[B, C]`` matrix is built exactly when one of the two routes
+  uses it (``needs_matrix``).  The fused kernels hold an embedding row in registers: dims above 128 take the matrix
+  (the reference accepts any dim).  A 2-D built-in loss without hard negatives is FUSED_2D whatever the row counts:
+  with more queries than candidates the C entry reports the error."""
+  has_metrics = len(batch_metric_classes) > 0
+  foreign_metrics = any(cls is not TopKCategoricalAccuracy for cls in batch_metric_classes)
+  options = sampling_correction or accidental_hits or score_mask     # what makes a logit more than a scaled dot product
+  mined_ok = not explicit and nc >= nq                               # the envelope of the tfrs_inbatch_mined_* entries
+
+  if custom_loss:
+    loss = LossRoute.CUSTOM
+  elif query_rank != 2:
+    fused = (query_rank == 3 and num_hard_negatives is None and dim <= 128 and 1 <= heads <= MAX_FUSED_HEADS
+             and not has_metrics)
+    loss = LossRoute.FUSED_MULTI_HEAD if fused else LossRoute.MATRIX_CE
+  elif dim > 128:
+    loss = LossRoute.MATRIX_CE
+  elif num_hard_negatives is None:
+    loss = LossRoute.FUSED_2D
+  elif not options and int(num_hard_negatives) + 2 <= 1024 and not has_metrics:
+    loss = LossRoute.TOPK_HARD_NEGATIVES
+  elif mined_ok and not foreign_metrics:        # a foreign batch metric needs the matrix anyway
+    loss = LossRoute.MINED
+  else:
+    loss = LossRoute.MATRIX_CE
+
+  if not has_metrics:
+    metric = MetricRoute.NONE
+  elif foreign_metrics:
+    metric = MetricRoute.MATRIX
+  elif loss is LossRoute.FUSED_2D and not temperature and not options:
+    metric = MetricRoute.PLAIN_COUNT
+  elif loss is LossRoute.MINED or (loss is LossRoute.FUSED_2D and mined_ok):
+    metric = MetricRoute.ADJUSTED_COUNT         # the temperature divides there as in the reference
+  else:
+    metric = MetricRoute.MATRIX
+  return loss, metric
+
+
+def needs_matrix(loss_route: LossRoute, metric_route: MetricRoute) -> bool:
+  return loss_route in (LossRoute.MATRIX_CE, LossRoute.CUSTOM) or metric_route is MetricRoute.MATRIX
 
 
 class Retrieval(torch.nn.Module, base.Task):
@@ -549,67 +621,36 @@ class Retrieval(torch.nn.Module, base.Task):
     # (captured step: the metric branch below forks HERE, in front of the loss kernels -- _streams.mark)
     fork_point = (_streams.mark(q.device) if compute_metrics and q.dim() == 2 and self._factorized_metrics else None)
 
-    # the fused kernels hold an embedding row in registers: dims above 128 (outside their
-    # envelope; the reference accepts any dim) take the explicit-logits path below
-    wide = q.dim() == 2 and q.shape[-1] > 128
-    has_batch_metrics = compute_batch_metrics and len(self._batch_metrics) > 0
-    adjusted = (self._temperature is not None or candidate_sampling_probability is not None
-                or self._remove_accidental_hits or score_mask is not None)
     # TFRS_RETRIEVAL_EXPLICIT=1 (read per call: tests and tools/bench_hard_negatives.py switch it) keeps hard
     # negatives / batch metrics over adjusted logits on the explicit [B, C] matrix, the comparator of the mined route
-    mined_ok = (os.environ.get("TFRS_RETRIEVAL_EXPLICIT") != "1" and self._loss is None and q.dim() == 2
-                and not wide and c.shape[0] >= q.shape[0])
-    counted_metrics = has_batch_metrics and all(type(m) is TopKCategoricalAccuracy for m in self._batch_metrics)
-    # batch metrics of unadjusted logits need a rank count per row, not the matrix (missing item 3 of
-    # round 3's review): tfrs_rank_count_accumulate on the plain dot products
-    fused_batch_metrics = (
-        counted_metrics and q.dim() == 2 and not wide and self._loss is None
-        and self._num_hard_negatives is None and not adjusted)
-    # hard-negative mining over plain (temperature-scaled) dot products: the top-K search names the rows
-    fused_hard_negatives = (
-        self._num_hard_negatives is not None and self._loss is None and q.dim() == 2 and not wide
-        and candidate_sampling_probability is None and not self._remove_accidental_hits
-        and score_mask is None and int(self._num_hard_negatives) + 2 <= 1024
-        and not has_batch_metrics)
-    # every other hard-negative configuration of the built-in loss: the radix select and the keep predicate inside
-    # the streaming kernels (mined_in_batch_softmax_loss) -- unless a foreign batch metric needs the matrix anyway
-    mined_hard_negatives = (
-        self._num_hard_negatives is not None and not fused_hard_negatives and mined_ok
-        and (counted_metrics or not has_batch_metrics))
-    # ... and batch metrics of ADJUSTED (or mined) logits: the rank count over the same logit function; the
-    # temperature divides there as in the reference, so near-ties merge as they do on the matrix
-    adjusted_batch_metrics = (
-        counted_metrics and not fused_batch_metrics and mined_ok
-        and (self._num_hard_negatives is None or mined_hard_negatives))
-    # multi-head queries: the fused max-sim kernels under the conditions of the 2-D fused route
-    fused_multi_head = (
-        q.dim() == 3 and self._loss is None and self._num_hard_negatives is None
-        and q.shape[-1] <= 128 and 1 <= q.shape[1] <= MAX_FUSED_HEADS
-        and not has_batch_metrics)
-    need_matrix = ((q.dim() == 3 and not fused_multi_head) or self._loss is not None
-                   or (self._num_hard_negatives is not None and not fused_hard_negatives
-                       and not mined_hard_negatives) or wide
-                   or (has_batch_metrics and not fused_batch_metrics and not adjusted_batch_metrics))
+    loss_route, metric_route = pick_routes(
+        custom_loss=self._loss is not None, query_rank=q.dim(), dim=q.shape[-1],
+        heads=q.shape[1] if q.dim() == 3 else 1, nq=q.shape[0], nc=c.shape[0],
+        num_hard_negatives=self._num_hard_negatives, temperature=self._temperature is not None,
+        sampling_correction=candidate_sampling_probability is not None,
+        accidental_hits=self._remove_accidental_hits, score_mask=score_mask is not None,
+        batch_metric_classes=[type(m) for m in self._batch_metrics] if compute_batch_metrics else [],
+        explicit=os.environ.get("TFRS_RETRIEVAL_EXPLICIT") == "1")
     scores = labels = None
-    if need_matrix:
+    if needs_matrix(loss_route, metric_route):
       scores, labels = self._logits_and_labels(
           q, c, candidate_sampling_probability, candidate_ids, score_mask)
 
     accidental_ids = candidate_ids if self._remove_accidental_hits else None
     tau = cut = None
-    if self._loss is None and q.dim() == 2 and self._num_hard_negatives is None and not wide:
+    if loss_route is LossRoute.FUSED_2D:
       loss = in_batch_softmax_loss(                                     # fused :172-210
           q, c, sample_weight, self._temperature, candidate_sampling_probability, accidental_ids, score_mask)
-    elif fused_multi_head:
+    elif loss_route is LossRoute.FUSED_MULTI_HEAD:
       loss = multi_head_in_batch_softmax_loss(                          # fused :172-176, :185-210
           q, c, sample_weight, self._temperature, candidate_sampling_probability, accidental_ids, score_mask)
-    elif fused_hard_negatives:
+    elif loss_route is LossRoute.TOPK_HARD_NEGATIVES:
       loss = hard_negative_softmax_loss(q, c, self._num_hard_negatives, sample_weight, self._temperature)
-    elif mined_hard_negatives:
+    elif loss_route is LossRoute.MINED:
       loss, tau, cut = _mined_softmax(                                  # fused :178-210 with :205-208
           q, c, self._num_hard_negatives, sample_weight, self._temperature, candidate_sampling_probability,
           accidental_ids, score_mask)
-    elif self._loss is None:
+    elif loss_route is LossRoute.MATRIX_CE:
       # CategoricalCrossentropy(from_logits, SUM) on the explicit logits (:86-87, :210): row-wise HIP kernels
       loss = logits_softmax_ce_sum(scores, labels, sample_weight)
     else:
@@ -628,9 +669,9 @@ class Retrieval(torch.nn.Module, base.Task):
     if compute_batch_metrics:                                           # :228-232
       with torch.no_grad():
         for metric in self._batch_metrics:
-          if fused_batch_metrics:
+          if metric_route is MetricRoute.PLAIN_COUNT:
             metric.update_from_embeddings(q, c, sample_weight=sample_weight)
-          elif adjusted_batch_metrics:
+          elif metric_route is MetricRoute.ADJUSTED_COUNT:
             metric.update_from_adjusted(q, c, sample_weight, self._temperature, candidate_sampling_probability,
                                         accidental_ids, score_mask, tau, cut)
           else:
