@@ -262,6 +262,14 @@ int tfrs_topk_update_from_scores(const float *scores, int64_t nq, int64_t nb, in
  * the Streaming reduce, :459-472): parts are scores[nparts, nq, k_in] /
  * idx[nparts, nq, k_in] (each sorted or not), result out[nq, k_out] under
  * (score desc, idx asc).  k_out <= nparts * k_in.
+ *
+ * Conventions shared by every list this selection layer reads or writes (tfrs_topk_merge*,
+ * tfrs_topk_update_from_scores, tfrs_topk_expand_duplicates; pinned by
+ * tests/test_select_layout_gpu.py): an entry whose idx is < 0 does not exist, whatever its score;
+ * -0.0 ties with +0.0 and comes back as +0.0; all k slots of a result are written, the ones
+ * past the last entry as (0.0f, -1).  A carried-in state holds its entries in its first
+ * state_len slots, sorted, without holes between them (trailing idx -1 slots are fine); slots
+ * at or past state_len are not read.
  * ------------------------------------------------------------------------- */
 size_t tfrs_topk_merge_workspace_bytes(int64_t nq, int nparts, int k_in, int k_out);
 int tfrs_topk_merge(const float *scores_parts, const int32_t *idx_parts, int nparts,
