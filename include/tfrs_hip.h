@@ -783,6 +783,28 @@ int tfrs_listwise_lambda_fwd(int kind, const float *labels, const float *scores,
                              int normalized, float smooth_fraction, float *loss, void *stream);
 int tfrs_listwise_lambda_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len, int topn,
                              int normalized, float smooth_fraction, const float *scale, float *dscores, void *stream);
+/* The pair-sum losses (losses.ApproxNDCGLoss / ApproxMRRLoss / UniqueSoftmaxLoss): every item first needs a
+ * sum over the other items of its list, and the gradient is a second pair sum over those.  One list, V the valid
+ * positions, n = |V|, alpha = float32(1 / temperature), sigma(x) = 1 / (1 + e^-x), sigma'(x) = sigma(x) sigma(-x),
+ * G_i = 2^{y_i} - 1, and the soft rank r_i = 1 + sum_{j in V, j != i} sigma(alpha (s_j - s_i)):
+ *   APPROX_NDCG     l = -(1 / IDCG) sum_V G_i / log2(1 + r_i), IDCG the ideal DCG of tfrs_listwise_ndcg without a cut;
+ *                   c_i = G_i / (IDCG ln2 (1 + r_i) log2(1 + r_i)^2)
+ *   APPROX_MRR      l = -(1 / Y) sum_V y_i / r_i, Y = sum_V y_i;  c_i = y_i / (Y r_i^2)
+ *                   both: dl/ds_k = alpha sum_{j in V, j != k} (c_j - c_k) sigma'(alpha (s_k - s_j)); l = 0 and every
+ *                   gradient +0 where IDCG <= 0 (Y <= 0)
+ *   UNIQUE_SOFTMAX  t = alpha s, lse_i = log(e^{t_i} + sum_{j in V: y_j < y_i} e^{t_j}), l = sum_V G_i (lse_i - t_i);
+ *                   dl/ds_k = alpha [G_k (e^{t_k - lse_k} - 1) + sum_{j in V: y_j > y_k} G_j e^{t_k - lse_j}]; finite
+ *                   for any finite scores (every lse is shifted by its own maximum)
+ * fwd: loss[l]; bwd: dscores[l, i] = scale[l] * dl/ds_i, recomputed from labels and scores alone.  Same envelope, same
+ * validity rule, one launch each on `stream`, no workspace, no atomics.  TFRS_EINVAL before any device call for an
+ * unknown kind, or a temperature that is not finite and positive or whose float32 reciprocal is not finite. */
+#define TFRS_LISTWISE_APPROX_NDCG 0
+#define TFRS_LISTWISE_APPROX_MRR 1
+#define TFRS_LISTWISE_UNIQUE_SOFTMAX 2
+int tfrs_listwise_pairsum_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                              float temperature, float *loss, void *stream);
+int tfrs_listwise_pairsum_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                              float temperature, const float *scale, float *dscores, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Cross.call (layers/feature_interaction/dcn.py:151-186), full rank, linear

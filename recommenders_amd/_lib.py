@@ -145,6 +145,8 @@ SIGNATURES = {
     "tfrs_listwise_metrics": (c_int, [P, P, c_i64, c_int, c_int, P, P, P, P, P]),
     "tfrs_listwise_lambda_fwd": (c_int, [c_int, P, P, c_i64, c_int, c_int, c_int, c_float, P, P]),
     "tfrs_listwise_lambda_bwd": (c_int, [c_int, P, P, c_i64, c_int, c_int, c_int, c_float, P, P, P]),
+    "tfrs_listwise_pairsum_fwd": (c_int, [c_int, P, P, c_i64, c_int, c_float, P, P]),
+    "tfrs_listwise_pairsum_bwd": (c_int, [c_int, P, P, c_i64, c_int, c_float, P, P, P]),
     "tfrs_cross_fwd": (c_int, [P, P, P, P, c_float, c_i64, c_int, P, P]),
     "tfrs_cross_fwd_ex": (c_int, [P, P, P, c_int, P, P, c_float, c_i64, c_int, P, P]),
     "tfrs_cross_bwd_workspace_bytes": (c_size_t, [c_i64, c_int, c_int]),

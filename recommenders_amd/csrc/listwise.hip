@@ -1,5 +1,6 @@
 // listwise.hip -- listwise ranking losses (softmax, pairwise logistic, pairwise hinge, ListMLE) with their gradients,
-// the two pairwise ones also with LambdaRank / LambdaLoss pair weights, and the per-list ranking metrics (NDCG, DCG, MRR,
+// the two pairwise ones also with LambdaRank / LambdaLoss pair weights, the three pair-sum losses (ApproxNDCG, ApproxMRR,
+// UniqueSoftmax), and the per-list ranking metrics (NDCG, DCG, MRR,
 // hits, precision, recall, MAP, ARP, OPA: all that a step asks for out of one launch), on [nlists, len] label / score
 // matrices (losses.py, metrics/listwise.py; formulas: DESIGN 4.24, 4.25, 4.26).
 //
@@ -51,6 +52,20 @@
 //                  IDCG <= 0).  Gains, discounts, ranks and (smooth) the table u(delta) = |D0(delta) - D0(delta + 1)|
 //                  live in the four scan buffers.  w_ij = |G_i - G_j| * |D_i - D_j|, or, smooth,
 //                  |G_i - G_j| * ((1 - mu) * |D_i - D_j| + mu * u(|r_i - r_j|)), evaluated in that order.
+//   pair sums      ApproxNDCG, ApproxMRR, UniqueSoftmax (listwise_pairsum_kernel; formulas: DESIGN 4.28): a first walk
+//                  whose per-item result feeds a second one.  alpha = 1 / temperature arrives as a float.
+//     soft rank    r_i = 1 + sum over j = 0, 1, ..., len - 1 (valid, j != i) in that order of sigma(alpha (s_j - s_i)), in
+//                  the thread that owns i, starting from 1; sigma and sigma' from e = exp(-|x|): one expf, one division.
+//     ApproxNDCG   IDCG as in NDCG (label sort, every rank); the list's loss is -(group sum of
+//                  (2^y_i - 1) / log2(1 + r_i)) / IDCG.  c_i = (2^y_i - 1) / (((IDCG ln2) (1 + r_i)) (lg lg)), lg = log2(1 + r_i).
+//     ApproxMRR    Y = group sum of y; the loss is -(group sum of y_i / r_i) / Y; c_i = y_i / ((Y r_i) r_i).
+//                  Both: 0 (and every gradient +0) where IDCG, Y <= 0.  Backward: c to a scan buffer, a barrier, then
+//                  g_k = alpha * sum over j = 0 .. len - 1 (valid, j != k) of (c_j - c_k) sigma'(alpha (s_k - s_j)).
+//     UniqueSoftmax  t = alpha s to a scan buffer.  Item i: m_i = max of t_i and the t_j with y_j < y_i (a walk of
+//                  compares), a_i = sum over j = 0 .. len - 1 (j == i or y_j < y_i) in that order of exp(t_j - m_i) >= 1,
+//                  lse_i = m_i + log a_i: finite for any finite scores.  Loss: group sum of (2^y_i - 1) (lse_i - t_i).
+//                  Backward: lse and 2^y - 1 to scan buffers, a barrier, then g_k = alpha * sum over j = 0 .. len - 1 of
+//                  G_k (exp(t_k - lse_k) - 1) at j == k and G_j exp(t_k - lse_j) where y_j > y_k (arguments <= 0).
 #include "common.h"
 
 namespace tfrs {
@@ -733,6 +748,194 @@ __global__ void __launch_bounds__(kLwThreads) listwise_lambda_kernel(int kind, c
   }
 }
 
+// ---- pair-sum losses (ApproxNDCG, ApproxMRR, UniqueSoftmax) ----------------------------------------------
+// A walk over j whose per-item result (soft rank, restricted logsumexp) feeds a second walk over j: the per-position
+// quantities of the second one cross the scan buffers, which these kinds leave free.
+enum { kPsApproxNdcg = TFRS_LISTWISE_APPROX_NDCG, kPsApproxMrr = TFRS_LISTWISE_APPROX_MRR,
+       kPsUniqueSoftmax = TFRS_LISTWISE_UNIQUE_SOFTMAX };
+constexpr float kLwLn2 = 0.693147180559945309f;
+
+// sigma(x) = 1 / (1 + exp(-x)) and sigma'(x) = sigma(x) sigma(-x) from e = exp(-|x|) <= 1: no overflow.
+__device__ __forceinline__ float lw_sigmoid(float x) {
+  const float e = expf(-fabsf(x));
+  return (x >= 0.0f ? 1.0f : e) / (1.0f + e);
+}
+__device__ __forceinline__ float lw_sigmoid_grad(float x) {
+  const float e = expf(-fabsf(x)), d = 1.0f + e;
+  return e / (d * d);
+}
+
+// r_i = 1 + sum_{j valid, j != i} sigma(alpha (s_j - s_i)) of the items a thread owns.
+template <int G>
+__device__ __forceinline__ void lw_soft_ranks(const LwList<G> &l, const LwShared<G> &sh, int len, float alpha, float *r) {
+  constexpr int IPT = LwCfg<G>::IPT;
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) r[c] = 1.0f;
+  for (int j = 0; j < len; ++j) {
+    const float yj = sh.y[l.off + j], sj = sh.s[l.off + j];
+    if (!(yj >= 0.0f)) continue;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c)
+      if (l.valid[c] && l.sub + G * c != j) r[c] += lw_sigmoid(alpha * (sj - l.sv[c]));
+  }
+}
+
+// lse_i = log(exp(t_i) + sum_{j valid, y_j < y_i} exp(t_j)) of the items a thread owns, t = the list's slots of a scan
+// buffer: the maximum first (compares), then the sum of exp(t_j - m_i), which holds exp(0) and so is >= 1.
+template <int G>
+__device__ __forceinline__ void lw_unique_lse(const LwList<G> &l, const LwShared<G> &sh, int len, const float *t,
+                                              float *ti, float *lse) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  float m[IPT], a[IPT];
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) {
+    ti[c] = t[l.sub + G * c];
+    m[c] = ti[c];
+    a[c] = 0.0f;
+  }
+  for (int j = 0; j < len; ++j) {
+    const float yj = sh.y[l.off + j], tj = t[j];
+    if (!(yj >= 0.0f)) continue;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c)
+      if (l.valid[c] && yj < l.yv[c]) m[c] = fmaxf(m[c], tj);
+  }
+  for (int j = 0; j < len; ++j) {
+    const float yj = sh.y[l.off + j], tj = t[j];
+    if (!(yj >= 0.0f)) continue;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c)
+      if (l.valid[c] && (yj < l.yv[c] || l.sub + G * c == j)) a[c] += expf(tj - m[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < IPT; ++c) lse[c] = l.valid[c] ? m[c] + logf(a[c]) : 0.0f;
+}
+
+template <int G, bool BWD>
+__global__ void __launch_bounds__(kLwThreads) listwise_pairsum_kernel(int kind, const float *__restrict__ labels,
+                                                                      const float *__restrict__ scores, int64_t nlists,
+                                                                      int len, int P, float alpha,
+                                                                      const float *__restrict__ scale,
+                                                                      float *__restrict__ out) {
+  constexpr int IPT = LwCfg<G>::IPT;
+  __shared__ LwShared<G> sh;
+  LwList<G> l;
+  lw_load<G>(l, sh, labels, scores, nlists, len);
+  const int64_t list = (int64_t)blockIdx.x * LwCfg<G>::LPB + threadIdx.x / G;
+  const float sc = (BWD && l.active) ? scale[list] : 0.0f;
+  float g[IPT];        // BWD: gradient of the item a thread owns, before alpha
+  float loss = 0.0f;   // !BWD: the list's loss
+  bool live = true;    // the list has a loss (approx kinds: IDCG, Y > 0)
+
+  if (kind == kPsUniqueSoftmax) {
+    float *t = sh.m[1] + l.off, *lsej = sh.m[0] + l.off, *gainj = sh.a[0] + l.off;
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) t[l.sub + G * c] = alpha * l.sv[c];
+    __syncthreads();
+    float ti[IPT], lse[IPT], gain[IPT];
+    lw_unique_lse<G>(l, sh, len, t, ti, lse);
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) gain[c] = l.valid[c] ? exp2f(l.yv[c]) - 1.0f : 0.0f;
+    if (!BWD) {
+      float v = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (l.valid[c]) v += gain[c] * (lse[c] - ti[c]);
+      loss = lw_sum<G>(v, sh.red);
+    } else {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        lsej[l.sub + G * c] = lse[c];
+        gainj[l.sub + G * c] = gain[c];
+        g[c] = 0.0f;
+      }
+      __syncthreads();
+      for (int j = 0; j < len; ++j) {
+        const float yj = sh.y[l.off + j], lj = lsej[j], gj = gainj[j];
+        if (!(yj >= 0.0f)) continue;
+#pragma unroll
+        for (int c = 0; c < IPT; ++c) {
+          if (!l.valid[c]) continue;
+          if (l.sub + G * c == j) g[c] += gj * (expf(ti[c] - lj) - 1.0f);
+          else if (yj > l.yv[c]) g[c] += gj * expf(ti[c] - lj);
+        }
+      }
+    }
+  } else {             // ApproxNDCG, ApproxMRR
+    float norm;        // IDCG, or Y
+    if (kind == kPsApproxNdcg) {
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int i = l.sub + G * c;
+        sh.key[l.off + i] = l.valid[c] ? make_key(l.yv[c], i) : 0ull;
+      }
+      __syncthreads();
+      lw_sort<G>(l, sh, P);
+      float v = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        const int r = l.sub + G * c;
+        const uint64_t k = r < P ? sh.key[l.off + r] : 0ull;
+        if (k != 0ull) v += (exp2f(sh.y[l.off + key_index(k)]) - 1.0f) / log2f((float)(r + 2));
+      }
+      norm = lw_sum<G>(v, sh.red);
+    } else {
+      float v = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) if (l.valid[c]) v += l.yv[c];
+      norm = lw_sum<G>(v, sh.red);
+    }
+    live = norm > 0.0f;
+    float r[IPT];
+    lw_soft_ranks<G>(l, sh, len, alpha, r);
+    if (!BWD) {
+      float v = 0.0f;
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        if (!l.valid[c]) continue;
+        if (kind == kPsApproxNdcg) v += (exp2f(l.yv[c]) - 1.0f) / log2f(1.0f + r[c]);
+        else v += l.yv[c] / r[c];
+      }
+      v = lw_sum<G>(v, sh.red);
+      loss = live ? -(v / norm) : 0.0f;
+    } else {
+      float *cj = sh.m[0] + l.off;
+      float ck[IPT];
+#pragma unroll
+      for (int c = 0; c < IPT; ++c) {
+        ck[c] = 0.0f;
+        if (l.valid[c] && live) {
+          if (kind == kPsApproxNdcg) {
+            const float lg = log2f(1.0f + r[c]);
+            ck[c] = (exp2f(l.yv[c]) - 1.0f) / (((norm * kLwLn2) * (1.0f + r[c])) * (lg * lg));
+          } else {
+            ck[c] = l.yv[c] / ((norm * r[c]) * r[c]);
+          }
+        }
+        cj[l.sub + G * c] = ck[c];
+        g[c] = 0.0f;
+      }
+      __syncthreads();
+      for (int j = 0; j < len; ++j) {
+        const float yj = sh.y[l.off + j], sj = sh.s[l.off + j], c_j = cj[j];
+        if (!(yj >= 0.0f)) continue;
+#pragma unroll
+        for (int c = 0; c < IPT; ++c)
+          if (l.valid[c] && l.sub + G * c != j) g[c] += (c_j - ck[c]) * lw_sigmoid_grad(alpha * (l.sv[c] - sj));
+      }
+    }
+  }
+
+  if (BWD) {
+#pragma unroll
+    for (int c = 0; c < IPT; ++c) {
+      const int i = l.sub + G * c;
+      if (l.active && i < len) out[l.base + i] = (l.valid[c] && live) ? sc * (alpha * g[c]) : 0.0f;
+    }
+  } else if (l.active && l.sub == 0) {
+    out[list] = loss;
+  }
+}
+
 static int lw_group(int len) { return len <= 8 ? 8 : len <= 16 ? 16 : len <= 32 ? 32 : len <= 64 ? 64 : 256; }
 static int lw_pow2(int len, int g) {
   int p = g < 256 ? g : 128;
@@ -768,6 +971,8 @@ static int lw_check_shape(const char *what, int64_t nlists, int len) {
 #define TFRS_LW_LAMBDA_FWD_SMOOTH(G) listwise_lambda_kernel<G, false, true>
 #define TFRS_LW_LAMBDA_BWD(G) listwise_lambda_kernel<G, true, false>
 #define TFRS_LW_LAMBDA_BWD_SMOOTH(G) listwise_lambda_kernel<G, true, true>
+#define TFRS_LW_PAIRSUM_FWD(G) listwise_pairsum_kernel<G, false>
+#define TFRS_LW_PAIRSUM_BWD(G) listwise_pairsum_kernel<G, true>
 
 static int lw_check_lambda(const char *what, int kind, int topn, float smooth_fraction) {
   TFRS_CHECK_ARG(kind == kLwPairLogistic || kind == kLwPairHinge,
@@ -775,6 +980,15 @@ static int lw_check_lambda(const char *what, int kind, int topn, float smooth_fr
   TFRS_CHECK_ARG(topn >= 0, "%s: topn=%d must be positive, or 0 for no cut", what, topn);
   TFRS_CHECK_ARG(smooth_fraction >= 0.0f && smooth_fraction <= 1.0f, "%s: smooth_fraction=%g outside [0, 1]", what,
                  (double)smooth_fraction);
+  return TFRS_OK;
+}
+
+// temperature finite and positive with a finite float32 reciprocal: alpha = 1 / temperature is what the kernels take.
+static int lw_check_pairsum(const char *what, int kind, float temperature) {
+  TFRS_CHECK_ARG(kind >= kPsApproxNdcg && kind <= kPsUniqueSoftmax, "%s: unknown kind %d", what, kind);
+  TFRS_CHECK_ARG(temperature > 0.0f && temperature <= 3.402823466e38f && 1.0f / temperature <= 3.402823466e38f,
+                 "%s: temperature=%g must be finite and positive, with a finite float32 reciprocal", what,
+                 (double)temperature);
   return TFRS_OK;
 }
 
@@ -896,6 +1110,33 @@ extern "C" int tfrs_listwise_lambda_bwd(int kind, const float *labels, const flo
   else
     TFRS_LW_DISPATCH(TFRS_LW_LAMBDA_BWD, kind, labels, scores, nlists, len, P, topn, normalized, smooth_fraction, scale,
                      dscores);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_pairsum_fwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                         float temperature, float *loss, void *stream) {
+  if (int rc = lw_check_pairsum("listwise_pairsum_fwd", kind, temperature)) return rc;
+  if (int rc = lw_check_shape("listwise_pairsum_fwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && loss, "listwise_pairsum_fwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const float alpha = 1.0f / temperature;
+  const float *no_scale = nullptr;
+  TFRS_LW_DISPATCH(TFRS_LW_PAIRSUM_FWD, kind, labels, scores, nlists, len, P, alpha, no_scale, loss);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_listwise_pairsum_bwd(int kind, const float *labels, const float *scores, int64_t nlists, int len,
+                                         float temperature, const float *scale, float *dscores, void *stream) {
+  if (int rc = lw_check_pairsum("listwise_pairsum_bwd", kind, temperature)) return rc;
+  if (int rc = lw_check_shape("listwise_pairsum_bwd", nlists, len)) return rc;
+  if (nlists == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(labels && scores && scale && dscores, "listwise_pairsum_bwd: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const float alpha = 1.0f / temperature;
+  TFRS_LW_DISPATCH(TFRS_LW_PAIRSUM_BWD, kind, labels, scores, nlists, len, P, alpha, scale, dscores);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }

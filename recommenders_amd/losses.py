@@ -256,3 +256,94 @@ class ListMLELoss(_ListwiseLoss):
 
   def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "list_mle_loss"):
     super().__init__(reduction, name)
+
+
+# ------------------------------------------------------------------------------------------------
+# Pair-sum losses: every item first needs a sum over the other items of its list (a soft rank, a
+# restricted logsumexp) and the gradient is a second pair sum over those; one fused kernel per direction
+# (csrc/listwise.hip: listwise_pairsum_kernel), no [B, L, L] tensor, the backward recomputes from the two inputs.
+# ------------------------------------------------------------------------------------------------
+_APPROX_NDCG, _APPROX_MRR, _UNIQUE_SOFTMAX = 0, 1, 2
+
+
+class _PairSumFn(torch.autograd.Function):
+  """Per-list loss ``[B]`` of one pair-sum kind over ``tfrs_listwise_pairsum_fwd`` / ``_bwd``; only the two inputs are
+  kept."""
+
+  @staticmethod
+  def forward(ctx, y_pred, y_true, kind, temperature):
+    from recommenders_amd import _lib
+    b, l = y_pred.shape
+    loss = torch.empty((b,), dtype=torch.float32, device=y_pred.device)
+    _lib.check(_lib.load().tfrs_listwise_pairsum_fwd(kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l, temperature,
+                                                      _lib.ptr(loss), _lib.current_stream()))
+    ctx.save_for_backward(y_true, y_pred)
+    ctx.args = (kind, temperature)
+    return loss
+
+  @staticmethod
+  def backward(ctx, grad):
+    from recommenders_amd import _lib
+    y_true, y_pred = ctx.saved_tensors
+    kind, temperature = ctx.args
+    b, l = y_pred.shape
+    scale = grad.to(torch.float32).contiguous()
+    ds = torch.empty_like(y_pred)
+    _lib.check(_lib.load().tfrs_listwise_pairsum_bwd(kind, _lib.ptr(y_true), _lib.ptr(y_pred), b, l, temperature,
+                                                      _lib.ptr(scale), _lib.ptr(ds), _lib.current_stream()))
+    return ds, None, None, None
+
+
+class _PairSumLoss(_ListwiseLoss):
+  """``temperature`` divides the scores (``alpha = float32(1 / temperature)``): it must be finite and positive and keep
+  that reciprocal finite.  Pads are selected out (TF-Ranking pushes them to ``min - 1e3`` / ``log 1e-10``); there is no
+  ``lambda_weight``, no per-item weight and no Gumbel variant."""
+
+  def __init__(self, reduction, name, temperature):
+    super().__init__(reduction, name)
+    try:
+      ok = not isinstance(temperature, bool) and 0.0 < float(temperature) < float("inf")      # (NaN fails both)
+      if ok:      # as float32, as the C entry sees it
+        t32 = torch.tensor(float(temperature), dtype=torch.float32)
+        ok = bool(t32 > 0) and bool(torch.isfinite(t32)) and bool(torch.isfinite(1.0 / t32))
+    except (TypeError, ValueError, OverflowError):
+      ok = False
+    if not ok:
+      raise ValueError(f"{type(self).__name__}: temperature must be finite and positive, with a finite float32 "
+                       f"reciprocal, got {temperature!r}")
+    self.temperature = float(temperature)
+
+  def _per_sample(self, y_true, y_pred):
+    return _PairSumFn.apply(y_pred, y_true, self._KIND, self.temperature)
+
+
+class ApproxNDCGLoss(_PairSumLoss):
+  """``-(1 / IDCG) sum_i (2^{y_i} - 1) / log2(1 + r_i)`` over the valid items of a list: NDCG with every hard rank
+  replaced by the soft rank ``r_i = 1 + sum_{j != i} sigmoid((s_j - s_i) / temperature)``.  ``IDCG`` is
+  ``NDCGMetric``'s ideal DCG over all ranks; a list whose ``IDCG`` is not positive has loss and gradient 0 (TF-Ranking
+  replaces such a list's labels by 1e-10)."""
+  _KIND = _APPROX_NDCG
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "approx_ndcg_loss",
+               temperature: float = 0.1):
+    super().__init__(reduction, name, temperature)
+
+
+class ApproxMRRLoss(_PairSumLoss):
+  """``-(1 / sum y) sum_i y_i / r_i`` over the valid items of a list, ``r_i`` the soft rank of ``ApproxNDCGLoss``; a
+  list whose labels sum to nothing positive has loss and gradient 0 (TF-Ranking gives it a non-zero value)."""
+  _KIND = _APPROX_MRR
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "approx_mrr_loss",
+               temperature: float = 0.1):
+    super().__init__(reduction, name, temperature)
+
+
+class UniqueSoftmaxLoss(_PairSumLoss):
+  """``sum_i (2^{y_i} - 1) (lse_i - t_i)`` over the valid items of a list, ``t = s / temperature`` and
+  ``lse_i = log(exp(t_i) + sum_{y_j < y_i} exp(t_j))``: every item competes only with the items labelled below it."""
+  _KIND = _UNIQUE_SOFTMAX
+
+  def __init__(self, reduction: str = "sum_over_batch_size", name: Optional[str] = "unique_softmax_loss",
+               temperature: float = 1.0):
+    super().__init__(reduction, name, temperature)

@@ -6,7 +6,9 @@ constructor and ``call`` arguments.  ``loss`` defaults to binary cross-entropy (
 Listwise ranking (the reference's listwise tutorial) needs nothing else from the task: with ``labels`` and
 ``predictions`` of shape ``[batch, list]`` (``-1`` labels pad a list) pass ``loss=losses.SoftmaxLoss()``,
 ``PairwiseLogisticLoss()``, ``PairwiseHingeLoss()`` or ``ListMLELoss()`` and ``metrics=[metrics.NDCGMetric(topn=...)]``;
-``sample_weight`` is then one weight per list.  The other list metrics go the same way (``MRRMetric``, ``HitsMetric``,
+``sample_weight`` is then one weight per list.  To train on the metric itself pass ``losses.ApproxNDCGLoss()`` or
+``ApproxMRRLoss()`` (the metric with every rank replaced by a sum of sigmoids, ``temperature=`` their width), or
+``UniqueSoftmaxLoss()`` for graded labels.  The other list metrics go the same way (``MRRMetric``, ``HitsMetric``,
 ``PrecisionMetric``, ``RecallMetric``, ``MeanAveragePrecisionMetric``, ``DCGMetric``, ``ARPMetric``, ``OPAMetric``); when
 two or more of ``metrics`` are list metrics the task updates them together, from one kernel launch that loads and sorts
 every list once (``metrics.update_listwise_metrics``), and everything else one by one as before."""
