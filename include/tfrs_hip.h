@@ -583,6 +583,41 @@ int tfrs_unified_embedding_fwd_multi(int n_units, const void *const *ids, int id
                                      const int32_t *chunk_index, int64_t *buckets, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * tf.keras.layers.IntegerLookup / StringLookup (the vocabulary layers in front of every Embedding of
+ * the reference's tutorials): token -> index through a device-resident hash table.
+ *
+ * table: `capacity` slots of 16 bytes {int64 key, int64 value}, 16-byte aligned; open addressing, linear
+ * probing, capacity a power of two >= 2 * n (anything else: TFRS_EINVAL).  A free slot holds
+ * TFRS_VOCAB_EMPTY_KEY, which is never stored: a token of that value is skipped by the build and
+ * answered by the lookup from `empty_value`.  No probe loop runs more than `capacity` steps.
+ *
+ * tfrs_vocab_build: clears the table and *flags (one launch), then inserts keys[i] -> i (one launch,
+ *   64-bit compare-and-swap on the key word).  *flags (device) afterwards: TFRS_VOCAB_DUPLICATE_KEY when
+ *   two keys are equal, TFRS_VOCAB_TABLE_FULL when a key found no slot.
+ * tfrs_vocab_lookup: ids[n] int32/int64 -> out[n] int64:
+ *     0                                      when has_mask and id == mask_key
+ *     base + value                           when the id is a key (or is TFRS_VOCAB_EMPTY_KEY and
+ *                                            empty_value >= 0; then value = empty_value)
+ *     oov_base + floormod(id, num_oov)       otherwise (oov_unsigned: the unsigned remainder);
+ *     -1                                     ... when num_oov == 0
+ *   *unknown_count (device, optional) += the number of ids of the last two kinds.  No synchronisation,
+ *   no allocation: capturable.
+ * tfrs_fingerprint_bytes: out[i] = SipHash-2-4 (all 64 bits, key bytes 00 01 .. 0f) of string i, packed as in
+ *   tfrs_hash_bucket_strong_bytes: the integer keys of StringLookup.
+ * ------------------------------------------------------------------------- */
+#define TFRS_VOCAB_EMPTY_KEY INT64_MIN
+#define TFRS_VOCAB_DUPLICATE_KEY 1u
+#define TFRS_VOCAB_TABLE_FULL 2u
+int tfrs_vocab_build(const int64_t *keys, int64_t n, void *table, int64_t capacity, uint32_t *flags,
+                     void *stream);
+int tfrs_vocab_lookup(const void *ids, int ids_are_i64, int64_t n, const void *table, int64_t capacity,
+                      int64_t n_tokens, int64_t base, int has_mask, int64_t mask_key, int64_t empty_value,
+                      int64_t oov_base, int64_t num_oov, int oov_unsigned, int64_t *unknown_count,
+                      int64_t *out, void *stream);
+int tfrs_fingerprint_bytes(const unsigned char *bytes, const int64_t *offsets, int64_t n, int64_t *out,
+                           void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Retrieval.call loss (tasks/retrieval.py:172-210, layers/loss.py:114-158):
  * in-batch sampled softmax without materialising the [nq, nc] logits.
  *   S = q c^T [/ temperature] [- log clip(p_c, 1e-6, 1)]

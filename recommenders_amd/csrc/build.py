@@ -38,6 +38,7 @@ SOURCES = [
     "table_update.hip",
     "shard_route.hip",
     "hashing.hip",
+    "vocab.hip",
     "softmax.hip",
     "softmax16.hip",
     "softmax_mined.hip",

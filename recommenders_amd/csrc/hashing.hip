@@ -127,6 +127,18 @@ __global__ void __launch_bounds__(256) hash_bytes_kernel(const unsigned char *__
                                   num_bins, recip);
 }
 
+// The full 64-bit SipHash-2-4 of every packed string under ONE fixed key (the SipHash paper's test key
+// 00 01 .. 0f): the keys of StringLookup's vocabulary table (vocab.hip).
+constexpr uint64_t kFingerprintK0 = 0x0706050403020100ull, kFingerprintK1 = 0x0f0e0d0c0b0a0908ull;
+
+__global__ void __launch_bounds__(256) fingerprint_bytes_kernel(const unsigned char *__restrict__ bytes,
+                                                                const int64_t *__restrict__ offsets,
+                                                                int64_t n, int64_t *__restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (int64_t)sip_of_bytes(bytes, offsets[i], offsets[i + 1], kFingerprintK0, kFingerprintK1);
+}
+
 // ---- fused UnifiedEmbedding lookup ---------------------------------------------------------
 // One launch per feature replaces num_chunks x (Hashing -> gather) + tf.concat
 // (unified_embedding.py:198-215).  Lookup p = value * C + chunk: lane-private SipHash of the
@@ -287,6 +299,17 @@ extern "C" int tfrs_hash_bucket_strong_bytes(const unsigned char *bytes, const i
   TFRS_CHECK_ARG(offsets && out, "hash_bucket_strong: NULL pointer");
   hipLaunchKernelGGL(hash_bytes_kernel, dim3(hash_grid(n)), dim3(256), 0, (hipStream_t)stream,
                      bytes, offsets, n, (uint64_t)num_bins, barrett_recip(num_bins), salt0, salt1, out);
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+extern "C" int tfrs_fingerprint_bytes(const unsigned char *bytes, const int64_t *offsets, int64_t n,
+                                      int64_t *out, void *stream) {
+  TFRS_CHECK_ARG(n >= 0, "fingerprint_bytes: bad count");
+  if (n == 0) return TFRS_OK;
+  TFRS_CHECK_ARG(bytes && offsets && out, "fingerprint_bytes: NULL pointer");
+  hipLaunchKernelGGL(fingerprint_bytes_kernel, dim3(hash_grid(n)), dim3(256), 0, (hipStream_t)stream, bytes,
+                     offsets, n, out);
   TFRS_LAUNCH_CHECK();
   return TFRS_OK;
 }
