@@ -1008,8 +1008,12 @@ int tfrs_dot_interaction_bwd(const float *x, const float *dout, int64_t batch, i
 /* Row-strided variants (packed-triangle output only): sample b's pairs live at out + b * out_stride
  * (dout + b * dout_stride), i.e. inside a wider [batch, out_stride] matrix -- lets the ranking model
  * write / read the block next to the bottom-stack output it is concatenated with
- * (experimental/models/ranking.py:225-232) without concat / slice copies.  TFRS_ENOTIMPL for shapes
- * outside the default kernels (fall back to the contiguous calls). */
+ * (experimental/models/ranking.py:225-232) without concat / slice copies.  The pair covers exactly
+ * batch >= 512, d = 16 or 32, f <= 122 with at least one pair, under the default switches (TFRS_DOT_STAGE=0,
+ * TFRS_DOT_FWD=staged / f32 and TFRS_DOT_BWD=dense / gather select kernels without a row stride); every other
+ * call returns TFRS_ENOTIMPL and writes nothing (fall back to the contiguous calls), also when out_stride
+ * equals the pair count.  The forward refuses wherever the backward would, so that a forward can never
+ * succeed without its backward; tfrs_dot_interaction_strided_supported answers beforehand. */
 int tfrs_dot_interaction_fwd_strided(const float *x, int64_t batch, int f, int d,
                                      int self_interaction, float *out, int64_t out_stride,
                                      void *stream);
@@ -1019,6 +1023,39 @@ int tfrs_dot_interaction_bwd_strided(const float *x, const float *dout, int64_t 
 /* 1 when BOTH strided entry points cover (batch, f, d): callers ask before they take the fused
  * concat path, so a forward can never succeed where its backward would return TFRS_ENOTIMPL. */
 int tfrs_dot_interaction_strided_supported(int64_t batch, int f, int d, int self_interaction);
+
+/* What the DotInteraction entry points would launch at a shape, answered by the decision function the
+ * launchers themselves switch on (DESIGN.md section 2 has the table).  Host only, no device work; reads
+ * TFRS_DOT_STAGE, TFRS_DOT_FWD, TFRS_DOT_BWD (and TFRS_DOT_FWD_GRID) as the launchers do.  strided = 1: the
+ * tfrs_dot_interaction_*_strided pair (no skip_gather: TFRS_EINVAL).
+ *   out   int64[32]: the forward route in [0..15], the backward route in [16..31], each
+ *         [0] kernel (TFRS_DOT_KERNEL_*)   [1] DP  [2] NB  [3] STAGE  [4] BLOCKS  [5] NFB  [6] MAXE
+ *         [7] NSTEP  [8] NEY  [9] NSET  (template arguments; 0 where the kernel has no such argument)
+ *         [10] workgroups  [11] threads per workgroup  [12] dynamic LDS bytes
+ *         [13] the dynamic LDS limit the launcher requests for the kernel (0: it requests none)
+ *         [14] half width of the backward's S tile (dense, producer / consumer)
+ *         [15] h16 backward: L words per buffer; fallback backward: samples per workgroup (4, 2 or 1).
+ * Forward TFRS_DOT_KERNEL_REFUSED (TFRS_ENOTIMPL from the entry point) is exactly
+ *   (f > 128 or d > 128 or ceil(f / 32) * DP / 2 > 128) and f * (d + 1) > 4096,   DP = d rounded up to 8, 16, 32, 64, 128;
+ * the backward refuses only f * d > 16384 outside f, d <= 128.  TFRS_DOT_KERNEL_NONE: no pairs (f = 1 without
+ * self interaction) -- the forward launches nothing (out may be NULL), the backward writes dx = 0 (dout may be NULL).
+ * tfrs_dot_interaction_plan_many: n rows of (batch, f, d, self_interaction, skip_gather, strided) -> n rows of
+ * int64[32], under one reading of the switches.  A shape below 1: TFRS_EINVAL. */
+#define TFRS_DOT_KERNEL_REFUSED 0
+#define TFRS_DOT_KERNEL_NONE 1
+#define TFRS_DOT_KERNEL_GATHER 2        /* dot_interaction_fwd_kernel / dot_interaction_bwd_kernel (fallback) */
+#define TFRS_DOT_KERNEL_MFMA_STAGED 3   /* dot_interaction_mfma_kernel<DP, NB, true> */
+#define TFRS_DOT_KERNEL_MFMA_DIRECT 4   /* dot_interaction_mfma_kernel<DP, NB, false> */
+#define TFRS_DOT_KERNEL_F16X3 5         /* dot_interaction_f16x3_kernel<DP, NB> */
+#define TFRS_DOT_KERNEL_F16X3_DIRECT 6  /* dot_interaction_f16x3_direct_kernel<DP, NB, BLOCKS> */
+#define TFRS_DOT_KERNEL_FWD_PC 7        /* dot_interaction_fwd_pc_kernel<NB, NSET> */
+#define TFRS_DOT_KERNEL_BWD_MFMA 8      /* dot_interaction_bwd_mfma_kernel<DP, NB> */
+#define TFRS_DOT_KERNEL_BWD_DENSE 9     /* dot_interaction_bwd_dense_kernel<NFB, MAXE> */
+#define TFRS_DOT_KERNEL_BWD_PC 10       /* dot_interaction_bwd_pc_kernel<MAXE> */
+#define TFRS_DOT_KERNEL_BWD_H16 11      /* dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET> */
+int tfrs_dot_interaction_plan(int64_t batch, int f, int d, int self_interaction, int skip_gather, int strided,
+                              int64_t *out);
+int tfrs_dot_interaction_plan_many(int64_t n, const int64_t *shapes, int64_t *out);
 
 /* ------------------------------------------------------------------------- *
  * ScaNN search (layers/factorized_top_k.py:613-796; csrc/scann.hip): partitioned, product-quantized approximate

@@ -176,6 +176,9 @@ SIGNATURES = {
     "tfrs_dot_interaction_fwd_strided": (c_int, [P, c_i64, c_int, c_int, c_int, P, c_i64, P]),
     "tfrs_dot_interaction_bwd_strided": (c_int, [P, P, c_i64, c_i64, c_int, c_int, c_int, P, P]),
     "tfrs_dot_interaction_strided_supported": (c_int, [c_i64, c_int, c_int, c_int]),
+    # host only: what the launchers would choose (int64[32]: forward route, backward route; tfrs_hip.h)
+    "tfrs_dot_interaction_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, P]),
+    "tfrs_dot_interaction_plan_many": (c_int, [c_i64, P, P]),
     "tfrs_scann_search_workspace_bytes": (c_size_t, [c_i64, c_int, c_int, c_int, c_i64, c_int]),
     "tfrs_scann_search": (c_int, [P, c_i64, c_int, P, P, c_int, P, c_int, c_i64, P, c_int, P, c_int, c_int, P, P,
                                   c_i64, c_int, c_int, P, P, P, c_size_t, P]),

@@ -288,7 +288,7 @@ __global__ void __launch_bounds__(256) dot_interaction_bwd_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;   // four, two or one sample per workgroup (LDS)
   if (b >= batch) return;
   float *xs = smem_f + (size_t)wave * f * d;
   const float *xb = x + b * (int64_t)f * d;
@@ -979,79 +979,289 @@ __global__ void __launch_bounds__(512, 4) dot_interaction_fwd_pc_kernel(const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// DotInteraction: the ONE host-side decision.  dot_decide_fwd / dot_decide_bwd say which kernel runs
+// at a shape, with which template arguments, grid and dynamic LDS; the launchers below switch on the
+// result, tfrs_dot_interaction_plan reports it and tfrs_dot_interaction_strided_supported asks it.
+// No launcher and no entry point holds a condition of its own.
+// ------------------------------------------------------------------------------------------
+enum DotKernel : int {
+  kDotRefused = 0,       // TFRS_ENOTIMPL
+  kDotNone = 1,          // no pairs (f == 1 without self interaction): nothing to launch, dx = 0
+  kDotGather = 2,        // dot_interaction_fwd_kernel / dot_interaction_bwd_kernel (fallback)
+  kDotMfmaStaged = 3,    // dot_interaction_mfma_kernel<DP, NB, true>
+  kDotMfmaDirect = 4,    // dot_interaction_mfma_kernel<DP, NB, false>
+  kDotF16x3 = 5,         // dot_interaction_f16x3_kernel<DP, NB>
+  kDotF16x3Direct = 6,   // dot_interaction_f16x3_direct_kernel<DP, NB, BLOCKS>
+  kDotFwdPc = 7,         // dot_interaction_fwd_pc_kernel<NB, NSET>
+  kDotBwdMfma = 8,       // dot_interaction_bwd_mfma_kernel<DP, NB>
+  kDotBwdDense = 9,      // dot_interaction_bwd_dense_kernel<NFB, MAXE>
+  kDotBwdPc = 10,        // dot_interaction_bwd_pc_kernel<MAXE>
+  kDotBwdH16 = 11,       // dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET>
+};
+
+struct DotRoute {
+  int kernel = kDotRefused;
+  int dp = 0, nb = 0, stage = 0, blocks = 0, nfb = 0, maxe = 0, nstep = 0, ney = 0, nset = 0;   // template arguments (0: not one)
+  int64_t grid = 0;
+  int threads = 0;
+  int64_t lds = 0;         // dynamic LDS bytes of the launch
+  int64_t lds_limit = 0;   // what the launcher asks ensure_dynamic_lds for (0: it does not ask)
+  int kh = 0;              // half width of the S tile (dense / producer-consumer backward)
+  int aux = 0;             // h16: L words per buffer; gather backward: samples (waves) per workgroup
+};
+
+struct DotSwitches {
+  const char *stage, *fwd, *bwd, *fwd_grid;
+};
+static DotSwitches dot_switches() {
+  return DotSwitches{option("TFRS_DOT_STAGE"), option("TFRS_DOT_FWD"), option("TFRS_DOT_BWD"), option("TFRS_DOT_FWD_GRID")};
+}
+
+constexpr int dot_pairs(int f, int self) { return self ? f * (f + 1) / 2 : f * (f - 1) / 2; }
+// register budget of the resident X: forward (NB fragments of DP / 2 registers) and gathered backward
+constexpr bool dot_fwd_resident(int DP, int nb) { return !(nb * (DP / 2) > 128); }
+constexpr bool dot_bwd_resident(int DP, int nb) { return !(nb * 16 * ((DP + 31) / 32) > 128); }
+// the split-fp16 forward kernels exist where raw + hi + lo operands stay in registers (beyond that they spill)
+constexpr bool dot_f16x3_fits(int DP, int nb) { return DP % 16 == 0 && nb * (DP / 2) <= 96; }
+constexpr int dot_maxe_bucket(int maxe) { return maxe <= 12 ? 12 : maxe <= 20 ? 20 : 33; }
+// L words per buffer of the h16 backward: the packed triangle of 16 NSTEP rows (reads of rows / columns beyond f stay
+// inside the zero region) + one 128-word row of slack for columns >= f
+constexpr int dot_bwd_h16_lwords(int nstep, int self) { return (dot_pairs(16 * nstep, self) + 128 + 3) & ~3; }
+
+static DotRoute dot_decide_bwd(int64_t batch, int f, int d, int self, int skip, int strided, const DotSwitches &sw);
+
+static DotRoute dot_decide_fwd(int64_t batch, int f, int d, int self, int skip, int strided, const DotSwitches &sw) {
+  DotRoute r;
+  const int out_dim = skip ? f * f : dot_pairs(f, self);
+  if (out_dim == 0) {   // no pairs: nothing to launch (and nothing to fuse into a wider matrix)
+    r.kernel = strided ? kDotRefused : kDotNone;
+    return r;
+  }
+  // a row stride: packed triangle only, on the widths the fused concat path is used at (d = 16, 32), and only
+  // where the strided backward runs too -- a forward must not succeed where its backward would refuse
+  if (strided && (skip || d % 16 != 0 || dot_decide_bwd(batch, f, d, self, skip, strided, sw).kernel == kDotRefused))
+    return DotRoute{};
+  const int nb = (f + 31) / 32;
+  if (f > 128 || d > 128 || !dot_fwd_resident(softmax_padded_dim(d), nb)) {
+    // fallback: four samples per workgroup, X staged in LDS with an odd row stride
+    const int64_t lds = (int64_t)4 * f * (d + 1) * (int64_t)sizeof(float);
+    if (strided || lds > 64 * 1024) return DotRoute{};
+    r.kernel = kDotGather;
+    r.grid = (batch + 3) / 4;
+    r.threads = 256;
+    r.lds = lds;
+    return r;
+  }
+  r.dp = softmax_padded_dim(d);
+  r.nb = nb;
+  const int64_t lds = (int64_t)(((out_dim + 3) & ~3) + 64) * (int64_t)sizeof(float);   // per wave
+  // TFRS_DOT_STAGE=0: direct 128-byte-run stores from the accumulators instead of the LDS-staged
+  // linear copy-out (measurement switch)
+  const bool stage = !skip && lds <= 64 * 1024 && !(sw.stage && sw.stage[0] == '0');
+  if (!stage) {
+    if (strided) return DotRoute{};   // only the split-fp16 direct-store kernels take a row stride
+    r.kernel = kDotMfmaDirect;
+    r.grid = std::min<int64_t>((batch + 3) / 4, 256 * 16);
+    r.threads = 256;
+    return r;
+  }
+  r.stage = 1;
+  const int64_t per_cu = std::min<int64_t>(8, std::max<int64_t>(1, (int64_t)(160 * 1024) / lds));
+  const int64_t staged_grid = std::min<int64_t>(batch, 256 * per_cu * 2);
+  // TFRS_DOT_FWD=f32 keeps the exact-f32 MFMA chain; =direct / =staged select the earlier split-fp16
+  // generations (measurement / comparison switches)
+  const char *fv = sw.fwd;
+  if (dot_f16x3_fits(r.dp, nb)) {
+    // default at d == 32: loads and stores on different waves
+    // (one row block, F <= 32, would leave three of the four product waves idle: 0.205 against 0.141 ms at F = 27)
+    if (!fv && d == 32 && nb >= 2 && batch >= 512) {
+      const int64_t lds_pc = (int64_t)2 * nb * 32 * 128 + 16 + (int64_t)2 * (((out_dim * 4 + 15) & ~15) + 1024);
+      r.kernel = kDotFwdPc;
+      r.stage = 0;
+      r.nset = 4;
+      r.grid = std::min<int64_t>(batch, sw.fwd_grid ? atoi(sw.fwd_grid) : 512);   // two workgroups per CU
+      r.threads = 512;
+      r.lds = lds_pc;
+      // (two row images of more than 5884 pairs -- F >= 109, or 108 with self interaction, up to 98.5 KiB at
+      // F = 128 -- are past the 80 KiB of two workgroups per CU: one workgroup per CU, and the request says so)
+      r.lds_limit = lds_pc <= 80 * 1024 ? 80 * 1024 : 160 * 1024;
+      return r;
+    }
+    if (!(fv && (fv[0] == 'f' || fv[0] == 's'))) {   // direct stores
+      // three workgroups per CU: 142 VGPRs, no scratch (four would spill 16 registers: 1.18 vs 1.06 ms)
+      r.kernel = kDotF16x3Direct;
+      r.stage = 0;
+      r.blocks = 3;
+      r.grid = std::min<int64_t>((batch + 3) / 4, 256 * 8);
+      r.threads = 256;
+      return r;
+    }
+    if (strided) return DotRoute{};
+    if (!(fv[0] == 'f' && fv[1] == '3')) {
+      r.kernel = kDotF16x3;
+      r.grid = staged_grid;
+      r.threads = 64;
+      r.lds = lds;
+      r.lds_limit = 64 * 1024;
+      return r;
+    }
+  }
+  if (strided) return DotRoute{};
+  r.kernel = kDotMfmaStaged;
+  r.grid = staged_grid;
+  r.threads = 64;
+  r.lds = lds;
+  r.lds_limit = 64 * 1024;
+  return r;
+}
+
+static DotRoute dot_decide_bwd(int64_t batch, int f, int d, int self, int skip, int strided, const DotSwitches &sw) {
+  DotRoute r;
+  const int out_dim = skip ? f * f : dot_pairs(f, self);
+  if (out_dim == 0) {   // no pairs: nothing to launch (and nothing to fuse into a wider matrix)
+    r.kernel = strided ? kDotRefused : kDotNone;
+    return r;
+  }
+  if (strided && (skip || d % 16 != 0)) return DotRoute{};
+  // default: split-fp16 kernel on the packed gradient (d == 32); TFRS_DOT_BWD=pc / dense / gather select
+  // the earlier generations (measurement switches; gather: the A operand gathered per element)
+  const char *dv = sw.bwd;
+  const bool packed = !skip && f <= 128 && d <= 128;
+  if (packed && !(dv && dv[0] == 'g')) {
+    int kh = (f + 7) / 8 * 4;                  // multiple of 4, 2 * kh >= f
+    if (((2 * kh + 4) / 4) % 2 == 0) kh += 4;  // odd number of 16-byte slots per row
+    const int64_t tile = (int64_t)f * (2 * kh + 4) + 256;   // S tile + 256 dummy slots
+    const int64_t lds = tile * (int64_t)sizeof(float);
+    if (lds <= 64 * 1024 && tile <= 0xFFFF) {
+      r.kh = kh;
+      const int maxe = (out_dim + 255) / 256;
+      if (!(dv && (dv[0] == 'd' || dv[0] == 'p')) && d == 32 && f >= 2 && batch >= 512 &&
+          out_dim >= 4) {                       // (a 16-byte load must fit inside a packed row)
+        const int nstep = (f + 15) / 16, ney = ((out_dim + 3) / 4 + 255) / 256;
+        if (ney <= 8) {                         // (f = 128 with self interaction: 8256 pairs)
+          if (nstep <= 4 && ney <= 3) r.nstep = 4, r.ney = 3, r.nset = 4;
+          else if (nstep <= 7 && ney <= 5) r.nstep = 7, r.ney = 5, r.nset = 4;
+          else if (nstep <= 7 && ney <= 6) r.nstep = 7, r.ney = 6, r.nset = 4;
+          else r.nstep = 8, r.ney = 8, r.nset = 3;
+          r.kernel = kDotBwdH16;
+          r.kh = 0;
+          r.aux = dot_bwd_h16_lwords(r.nstep, self);
+          r.grid = std::min<int64_t>(batch, 256);
+          r.threads = 512;
+          r.lds = ((int64_t)2 * (r.aux + 16 * r.nstep * 32) + 8) * (int64_t)sizeof(uint32_t);
+          r.lds_limit = 160 * 1024;
+          return r;
+        }
+      }
+      const int64_t lds_pc = 2 * lds + (int64_t)2 * (2 * kh * 32) * (int64_t)sizeof(float);
+      if (!(dv && dv[0] == 'd') && d <= 32 && lds_pc <= 160 * 1024 && batch >= 512) {
+        // producer / consumer kernel: one 8-wave workgroup per CU, double-buffered S and X tiles
+        r.kernel = kDotBwdPc;
+        r.maxe = dot_maxe_bucket(maxe);
+        r.grid = std::min<int64_t>(batch, 256);
+        r.threads = 512;
+        r.lds = lds_pc;
+        r.lds_limit = 160 * 1024;
+        return r;
+      }
+      if (strided) return DotRoute{};   // only the h16 and the producer / consumer kernel take a row stride
+      const int64_t per_cu = std::min<int64_t>(2, std::max<int64_t>(1, (int64_t)(160 * 1024) / lds));
+      const int nfb = (d + 31) / 32;
+      r.kernel = kDotBwdDense;
+      r.nfb = nfb <= 2 ? nfb : 4;
+      r.maxe = dot_maxe_bucket(maxe);
+      r.grid = std::min<int64_t>(batch, 256 * per_cu);
+      r.threads = 256;
+      r.lds = lds;
+      r.lds_limit = 64 * 1024;
+      return r;
+    }
+  }
+  if (strided) return DotRoute{};
+  if (packed) {
+    const int dp = softmax_padded_dim(d), nb = (f + 31) / 32;
+    const int64_t lds = (int64_t)((out_dim + 3) & ~3) * (int64_t)sizeof(float);
+    if (dot_bwd_resident(dp, nb) && lds <= 64 * 1024) {
+      const int64_t per_cu = std::min<int64_t>(8, std::max<int64_t>(1, (int64_t)(160 * 1024) / lds));
+      r.kernel = kDotBwdMfma;
+      r.dp = dp;
+      r.nb = nb;
+      r.grid = std::min<int64_t>(batch, 256 * per_cu * 2);
+      r.threads = 64;
+      r.lds = lds;
+      r.lds_limit = 64 * 1024;
+      return r;
+    }
+  }
+  // fallback: X staged in LDS, one wave per sample; four samples per workgroup where they fit 64 KiB, else two or one
+  // (skip_gather has no other backward, and its forward covers every f, d <= 128 of the resident kernels)
+  const int64_t per_sample = (int64_t)f * d * (int64_t)sizeof(float);
+  int waves = 4;
+  while (waves > 1 && waves * per_sample > 64 * 1024) waves >>= 1;
+  if (waves * per_sample > 64 * 1024) return DotRoute{};
+  r.kernel = kDotGather;
+  r.aux = waves;
+  r.grid = (batch + waves - 1) / waves;
+  r.threads = 64 * waves;
+  r.lds = waves * per_sample;
+  return r;
+}
+
 template <int NB>
-static void launch_dot_fwd_pc(const float *x, int64_t batch, int f, int self, float *out, hipStream_t s,
-                              int64_t out_stride) {
-  const int out_dim_ = self ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  const size_t lds = (size_t)2 * NB * 32 * 128 + 16 + (size_t)2 * (((out_dim_ * 4 + 15) & ~15) + 1024);
-  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_fwd_pc_kernel<NB, 4>), 80 * 1024);
-  const char *gv = option("TFRS_DOT_FWD_GRID");
-  const dim3 grid((unsigned)std::min<int64_t>(batch, gv ? atoi(gv) : 512));   // two workgroups per CU
-  hipLaunchKernelGGL((dot_interaction_fwd_pc_kernel<NB, 4>), grid, dim3(512), lds, s, x, batch, f, self, out, out_stride);
+static void launch_dot_fwd_pc(const DotRoute &r, const float *x, int64_t batch, int f, int self, float *out,
+                              hipStream_t s, int64_t out_stride) {
+  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_fwd_pc_kernel<NB, 4>), (int)r.lds_limit);
+  hipLaunchKernelGGL((dot_interaction_fwd_pc_kernel<NB, 4>), dim3((unsigned)r.grid), dim3(512), (size_t)r.lds, s, x,
+                     batch, f, self, out, out_stride);
 }
 
 template <int DP, int NB>
-static bool launch_dot_mfma_nb(const float *x, int64_t batch, int f, int d, int self, int skip,
+static bool launch_dot_mfma_nb(const DotRoute &r, const float *x, int64_t batch, int f, int d, int self, int skip,
                                float *out, hipStream_t s, int64_t out_stride) {
-  const int out_dim = skip ? f * f : (self ? f * (f + 1) / 2 : f * (f - 1) / 2);
-  const bool strided = out_stride != 0 && out_stride != out_dim;   // only the direct-store kernel takes a row stride
-  const size_t lds = (size_t)(((out_dim + 3) & ~3) + 64) * sizeof(float);  // per wave
-  // TFRS_DOT_STAGE=0: direct 128-byte-run stores from the accumulators instead of the LDS-staged
-  // linear copy-out (measurement switch)
-  const char *sv = option("TFRS_DOT_STAGE");
-  const bool stage = !skip && lds <= 64 * 1024 && !(sv && sv[0] == '0');
-  if (stage) {
-    (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_mfma_kernel<DP, NB, true>), 64 * 1024);
-    const int64_t per_cu = std::min<int64_t>(8, std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds));
-    const dim3 grid((unsigned)std::min<int64_t>(batch, 256 * per_cu * 2));
-    // TFRS_DOT_FWD=f32 keeps the exact-f32 MFMA chain (measurement / comparison switch)
-    const char *fv = option("TFRS_DOT_FWD");
-    if constexpr (DP % 16 == 0 && NB * (DP / 2) <= 96) {   // (beyond that the raw + hi + lo operands spill)
-      if constexpr (DP == 32) {
-        // default at d == 32: loads and stores on different waves; TFRS_DOT_FWD=direct / staged / f32 select
-        // the earlier generations (measurement switches)
-        // (one row block, F <= 32, would leave three of the four product waves idle: 0.205 against 0.141 ms at F = 27)
-        if (!fv && d == 32 && NB >= 2 && batch >= 512) {
-          launch_dot_fwd_pc<NB>(x, batch, f, self, out, s, strided ? out_stride : (int64_t)out_dim);
-          return true;
-        }
-      }
-      if (!(fv && (fv[0] == 'f' || fv[0] == 's'))) {   // direct stores
-        const dim3 gd((unsigned)std::min<int64_t>((batch + 3) / 4, 256 * 8));
-        // three workgroups per CU: 142 VGPRs, no scratch (four would spill 16 registers: 1.18 vs 1.06 ms)
-        hipLaunchKernelGGL((dot_interaction_f16x3_direct_kernel<DP, NB, 3>), gd, dim3(256), 0, s, x, batch, f, d, self, out,
-                           strided ? out_stride : (int64_t)out_dim);
-        return true;
-      }
-      if (strided) return false;
-      if (!(fv && fv[0] == 'f' && fv[1] == '3')) {
-        (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_f16x3_kernel<DP, NB>), 64 * 1024);
-        hipLaunchKernelGGL((dot_interaction_f16x3_kernel<DP, NB>), grid, dim3(64), lds, s, x, batch, f, d, self, out);
+  // (out_stride: the row stride of the kernels that take one -- the caller passes the pair count for a contiguous output)
+  const dim3 grid((unsigned)r.grid), block((unsigned)r.threads);
+  const size_t lds = (size_t)r.lds;
+  if constexpr (dot_f16x3_fits(DP, NB)) {   // (the split-fp16 kernels are instantiated where the decision can choose them)
+    if constexpr (DP == 32) {
+      if (r.kernel == kDotFwdPc) {
+        launch_dot_fwd_pc<NB>(r, x, batch, f, self, out, s, out_stride);
         return true;
       }
     }
-    if (strided) return false;
-    hipLaunchKernelGGL((dot_interaction_mfma_kernel<DP, NB, true>), grid, dim3(64), lds, s, x, batch, f, d,
-                       self, skip, out);
-  } else {
-    if (strided) return false;
-    const dim3 grid((unsigned)std::min<int64_t>((batch + 3) / 4, 256 * 16));
-    hipLaunchKernelGGL((dot_interaction_mfma_kernel<DP, NB, false>), grid, dim3(256), 0, s, x, batch, f, d,
-                       self, skip, out);
+    if (r.kernel == kDotF16x3Direct) {
+      hipLaunchKernelGGL((dot_interaction_f16x3_direct_kernel<DP, NB, 3>), grid, block, lds, s, x, batch, f, d, self, out,
+                         out_stride);
+      return true;
+    }
+    if (r.kernel == kDotF16x3) {
+      (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_f16x3_kernel<DP, NB>), (int)r.lds_limit);
+      hipLaunchKernelGGL((dot_interaction_f16x3_kernel<DP, NB>), grid, block, lds, s, x, batch, f, d, self, out);
+      return true;
+    }
   }
-  return true;
+  if (r.kernel == kDotMfmaStaged) {
+    (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_mfma_kernel<DP, NB, true>), (int)r.lds_limit);
+    hipLaunchKernelGGL((dot_interaction_mfma_kernel<DP, NB, true>), grid, block, lds, s, x, batch, f, d,
+                       self, skip, out);
+    return true;
+  }
+  if (r.kernel == kDotMfmaDirect) {
+    hipLaunchKernelGGL((dot_interaction_mfma_kernel<DP, NB, false>), grid, block, lds, s, x, batch, f, d,
+                       self, skip, out);
+    return true;
+  }
+  return false;   // a route without a kernel: an error, never another kernel
 }
 
 template <int DP>
-static bool launch_dot_mfma_dp(const float *x, int64_t batch, int f, int d, int self, int skip,
+static bool launch_dot_mfma_dp(const DotRoute &r, const float *x, int64_t batch, int f, int d, int self, int skip,
                                float *out, hipStream_t s, int64_t out_stride) {
-  const int nb = (f + 31) / 32;
-  if (nb * (DP / 2) > 128) return false;  // register budget of the resident X
-  switch (nb) {
-    case 1: return launch_dot_mfma_nb<DP, 1>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 2: return launch_dot_mfma_nb<DP, 2>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 3: return launch_dot_mfma_nb<DP, 3>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 4: return launch_dot_mfma_nb<DP, 4>(x, batch, f, d, self, skip, out, s, out_stride);
+  switch (r.nb) {
+    case 1: return launch_dot_mfma_nb<DP, 1>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 2: return launch_dot_mfma_nb<DP, 2>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 3: return launch_dot_mfma_nb<DP, 3>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 4: return launch_dot_mfma_nb<DP, 4>(r, x, batch, f, d, self, skip, out, s, out_stride);
     default: return false;
   }
 }
@@ -1747,157 +1957,185 @@ __global__ void __launch_bounds__(512) dot_interaction_bwd_h16_kernel(
   }
 }
 
-// L words per buffer: the packed triangle of 16 NSTEP rows (reads of rows / columns beyond f stay
-// inside the zero region) + one 128-word row of slack for columns >= f
-static int dot_bwd_h16_lwords(int nstep, int self) {
-  const int n = 16 * nstep;
-  return ((self ? n * (n + 1) / 2 : n * (n - 1) / 2) + 128 + 3) & ~3;
-}
-
 template <int NSTEP, int NEY, int NSET>
-static void launch_dot_bwd_h16_v(const float *x, const float *dout, int64_t batch, int f, int self, dim3 grid,
+static void launch_dot_bwd_h16_v(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int self,
                                  float *dx, hipStream_t s, int64_t dout_stride) {
-  const int lwords = dot_bwd_h16_lwords(NSTEP, self);
-  const size_t lds = ((size_t)2 * (lwords + 16 * NSTEP * 32) + 8) * sizeof(uint32_t);
-  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET>), 160 * 1024);
-  hipLaunchKernelGGL((dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET>), grid, dim3(512), lds, s, x, dout, batch, f,
-                     self, lwords, dx, dout_stride);
+  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET>), (int)r.lds_limit);
+  hipLaunchKernelGGL((dot_interaction_bwd_h16_kernel<NSTEP, NEY, NSET>), dim3((unsigned)r.grid), dim3((unsigned)r.threads),
+                     (size_t)r.lds, s, x, dout, batch, f, self, r.aux, dx, dout_stride);
 }
 
-// d == 32, f <= 128: which instantiation covers (f, self), or false
-static bool launch_dot_bwd_h16(const float *x, const float *dout, int64_t batch, int f, int d, int self,
-                               float *dx, hipStream_t s, int64_t dout_stride, bool probe_only = false) {
-  if (d != 32 || f < 2 || f > 128 || batch < 512) return false;
-  const int out_dim = self ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  if (out_dim < 4) return false;               // (a 16-byte load must fit inside a packed row)
-  const int nstep = (f + 15) / 16, ney = ((out_dim + 3) / 4 + 255) / 256;
-  if (ney > 8) return false;                   // f = 128 with self interaction: 8256 pairs
-  if (probe_only) return true;
-  const dim3 grid((unsigned)std::min<int64_t>(batch, 256));
-  const int64_t st = dout_stride ? dout_stride : (int64_t)out_dim;
-  if (nstep <= 4 && ney <= 3) launch_dot_bwd_h16_v<4, 3, 4>(x, dout, batch, f, self, grid, dx, s, st);
-  else if (nstep <= 7 && ney <= 5) launch_dot_bwd_h16_v<7, 5, 4>(x, dout, batch, f, self, grid, dx, s, st);
-  else if (nstep <= 7 && ney <= 6) launch_dot_bwd_h16_v<7, 6, 4>(x, dout, batch, f, self, grid, dx, s, st);
-  else launch_dot_bwd_h16_v<8, 8, 3>(x, dout, batch, f, self, grid, dx, s, st);
-  return true;
-}
-
-template <int MAXE>
-static void launch_dot_bwd_pc_v(const float *x, const float *dout, int64_t batch, int f, int d, int self,
-                                int kh, size_t lds, dim3 grid, float *dx, hipStream_t s, int64_t dout_stride) {
-  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_pc_kernel<MAXE>), 160 * 1024);
-  hipLaunchKernelGGL((dot_interaction_bwd_pc_kernel<MAXE>), grid, dim3(512), lds, s, x, dout, batch, f, d,
-                     self, kh, dx, dout_stride);
-}
-
-static void launch_dot_bwd_pc_e(int maxe, const float *x, const float *dout, int64_t batch, int f, int d,
-                                int self, int kh, size_t lds, dim3 grid, float *dx, hipStream_t s,
-                                int64_t dout_stride) {
-  if (maxe <= 12) launch_dot_bwd_pc_v<12>(x, dout, batch, f, d, self, kh, lds, grid, dx, s, dout_stride);
-  else if (maxe <= 20) launch_dot_bwd_pc_v<20>(x, dout, batch, f, d, self, kh, lds, grid, dx, s, dout_stride);
-  else launch_dot_bwd_pc_v<33>(x, dout, batch, f, d, self, kh, lds, grid, dx, s, dout_stride);
-}
-
-template <int NFB, int MAXE>
-static void launch_dot_bwd_dense_v(const float *x, const float *dout, int64_t batch, int f, int d,
-                                   int self, int kh, size_t lds, dim3 grid, float *dx, hipStream_t s) {
-  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_dense_kernel<NFB, MAXE>), 64 * 1024);
-  hipLaunchKernelGGL((dot_interaction_bwd_dense_kernel<NFB, MAXE>), grid, dim3(256), lds, s, x, dout, batch,
-                     f, d, self, kh, dx);
-}
-
-template <int NFB>
-static void launch_dot_bwd_dense_e(int maxe, const float *x, const float *dout, int64_t batch, int f,
-                                   int d, int self, int kh, size_t lds, dim3 grid, float *dx,
-                                   hipStream_t s) {
-  if (maxe <= 12) launch_dot_bwd_dense_v<NFB, 12>(x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-  else if (maxe <= 20) launch_dot_bwd_dense_v<NFB, 20>(x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-  else launch_dot_bwd_dense_v<NFB, 33>(x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-}
-
-static bool launch_dot_bwd_dense(const float *x, const float *dout, int64_t batch, int f, int d,
-                                 int self, float *dx, hipStream_t s, int64_t dout_stride = 0) {
-  if (f > 128 || d > 128) return false;
-  int kh = (f + 7) / 8 * 4;                  // multiple of 4, 2 * kh >= f
-  if (((2 * kh + 4) / 4) % 2 == 0) kh += 4;  // odd number of 16-byte slots per row
-  const size_t lds = ((size_t)f * (2 * kh + 4) + 256) * sizeof(float);   // tile + 256 dummy slots
-  if (lds > 64 * 1024 || (size_t)f * (2 * kh + 4) + 256 > 0xFFFFu) return false;
-  const int out_dim = self ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  const int maxe = (out_dim + 255) / 256;
-  const char *dv = option("TFRS_DOT_BWD");
-  // default: split-fp16 kernel on the packed gradient (d == 32); TFRS_DOT_BWD=pc / dense / gather select
-  // the earlier generations (measurement switches)
-  if (!(dv && (dv[0] == 'd' || dv[0] == 'p')) &&
-      launch_dot_bwd_h16(x, dout, batch, f, d, self, dx, s, dout_stride))
-    return true;
-  const size_t lds_pc = 2 * lds + (size_t)2 * (2 * kh * 32) * sizeof(float);
-  if (!(dv && dv[0] == 'd') && d <= 32 && lds_pc <= 160 * 1024 && batch >= 512) {
-    // producer / consumer kernel: one 8-wave workgroup per CU, double-buffered S and X tiles
-    const dim3 grid_pc((unsigned)std::min<int64_t>(batch, 256));
-    launch_dot_bwd_pc_e(maxe, x, dout, batch, f, d, self, kh, lds_pc, grid_pc, dx, s,
-                        dout_stride ? dout_stride : (int64_t)out_dim);
-    return true;
-  }
-  if (dout_stride != 0 && dout_stride != out_dim) return false;   // only the producer / consumer kernel takes a row stride
-  const int64_t per_cu = std::min<int64_t>(2, std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds));
-  const dim3 grid((unsigned)std::min<int64_t>(batch, 256 * per_cu));
-  const int nfb = (d + 31) / 32;
-  if (nfb == 1) launch_dot_bwd_dense_e<1>(maxe, x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-  else if (nfb == 2) launch_dot_bwd_dense_e<2>(maxe, x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-  else launch_dot_bwd_dense_e<4>(maxe, x, dout, batch, f, d, self, kh, lds, grid, dx, s);
-  return true;
-}
-
-template <int DP, int NB>
-static bool launch_dot_bwd_mfma_nb(const float *x, const float *dout, int64_t batch, int f, int d,
-                                   int self, float *dx, hipStream_t s) {
-  const int out_dim = self ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  const size_t lds = (size_t)((out_dim + 3) & ~3) * sizeof(float);
-  if (lds > 64 * 1024) return false;
-  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_mfma_kernel<DP, NB>), 64 * 1024);
-  const int64_t per_cu = std::min<int64_t>(8, std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds));
-  const dim3 grid((unsigned)std::min<int64_t>(batch, 256 * per_cu * 2));
-  hipLaunchKernelGGL((dot_interaction_bwd_mfma_kernel<DP, NB>), grid, dim3(64), lds, s, x, dout, batch, f,
-                     d, self, dx);
-  return true;
-}
-
-template <int DP>
-static bool launch_dot_bwd_mfma_dp(const float *x, const float *dout, int64_t batch, int f, int d,
-                                   int self, float *dx, hipStream_t s) {
-  const int nb = (f + 31) / 32;
-  if (nb * 16 * ((DP + 31) / 32) > 128) return false;  // register budget of the resident X operand
-  switch (nb) {
-    case 1: return launch_dot_bwd_mfma_nb<DP, 1>(x, dout, batch, f, d, self, dx, s);
-    case 2: return launch_dot_bwd_mfma_nb<DP, 2>(x, dout, batch, f, d, self, dx, s);
-    case 3: return launch_dot_bwd_mfma_nb<DP, 3>(x, dout, batch, f, d, self, dx, s);
-    case 4: return launch_dot_bwd_mfma_nb<DP, 4>(x, dout, batch, f, d, self, dx, s);
+static bool launch_dot_bwd_h16(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int self,
+                               float *dx, hipStream_t s, int64_t st) {
+  switch (r.nstep * 100 + r.ney * 10 + r.nset) {
+    case 434: launch_dot_bwd_h16_v<4, 3, 4>(r, x, dout, batch, f, self, dx, s, st); return true;
+    case 754: launch_dot_bwd_h16_v<7, 5, 4>(r, x, dout, batch, f, self, dx, s, st); return true;
+    case 764: launch_dot_bwd_h16_v<7, 6, 4>(r, x, dout, batch, f, self, dx, s, st); return true;
+    case 883: launch_dot_bwd_h16_v<8, 8, 3>(r, x, dout, batch, f, self, dx, s, st); return true;
     default: return false;
   }
 }
 
-static bool launch_dot_bwd_mfma(const float *x, const float *dout, int64_t batch, int f, int d,
-                                int self, float *dx, hipStream_t s) {
-  if (d > 128 || f > 128) return false;
-  switch (softmax_padded_dim(d)) {
-    case 8: return launch_dot_bwd_mfma_dp<8>(x, dout, batch, f, d, self, dx, s);
-    case 16: return launch_dot_bwd_mfma_dp<16>(x, dout, batch, f, d, self, dx, s);
-    case 32: return launch_dot_bwd_mfma_dp<32>(x, dout, batch, f, d, self, dx, s);
-    case 64: return launch_dot_bwd_mfma_dp<64>(x, dout, batch, f, d, self, dx, s);
-    default: return launch_dot_bwd_mfma_dp<128>(x, dout, batch, f, d, self, dx, s);
+template <int MAXE>
+static void launch_dot_bwd_pc_v(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                int self, float *dx, hipStream_t s, int64_t dout_stride) {
+  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_pc_kernel<MAXE>), (int)r.lds_limit);
+  hipLaunchKernelGGL((dot_interaction_bwd_pc_kernel<MAXE>), dim3((unsigned)r.grid), dim3((unsigned)r.threads),
+                     (size_t)r.lds, s, x, dout, batch, f, d, self, r.kh, dx, dout_stride);
+}
+
+static bool launch_dot_bwd_pc(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                              int self, float *dx, hipStream_t s, int64_t st) {
+  switch (r.maxe) {
+    case 12: launch_dot_bwd_pc_v<12>(r, x, dout, batch, f, d, self, dx, s, st); return true;
+    case 20: launch_dot_bwd_pc_v<20>(r, x, dout, batch, f, d, self, dx, s, st); return true;
+    case 33: launch_dot_bwd_pc_v<33>(r, x, dout, batch, f, d, self, dx, s, st); return true;
+    default: return false;
   }
 }
 
-static bool launch_dot_mfma(const float *x, int64_t batch, int f, int d, int self, int skip,
-                            float *out, hipStream_t s, int64_t out_stride = 0) {
-  if (d > 128 || f > 128) return false;
-  switch (softmax_padded_dim(d)) {
-    case 8: return launch_dot_mfma_dp<8>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 16: return launch_dot_mfma_dp<16>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 32: return launch_dot_mfma_dp<32>(x, batch, f, d, self, skip, out, s, out_stride);
-    case 64: return launch_dot_mfma_dp<64>(x, batch, f, d, self, skip, out, s, out_stride);
-    default: return launch_dot_mfma_dp<128>(x, batch, f, d, self, skip, out, s, out_stride);
+template <int NFB, int MAXE>
+static void launch_dot_bwd_dense_v(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                   int self, float *dx, hipStream_t s) {
+  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_dense_kernel<NFB, MAXE>), (int)r.lds_limit);
+  hipLaunchKernelGGL((dot_interaction_bwd_dense_kernel<NFB, MAXE>), dim3((unsigned)r.grid), dim3((unsigned)r.threads),
+                     (size_t)r.lds, s, x, dout, batch, f, d, self, r.kh, dx);
+}
+
+template <int NFB>
+static bool launch_dot_bwd_dense_e(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f,
+                                   int d, int self, float *dx, hipStream_t s) {
+  switch (r.maxe) {
+    case 12: launch_dot_bwd_dense_v<NFB, 12>(r, x, dout, batch, f, d, self, dx, s); return true;
+    case 20: launch_dot_bwd_dense_v<NFB, 20>(r, x, dout, batch, f, d, self, dx, s); return true;
+    case 33: launch_dot_bwd_dense_v<NFB, 33>(r, x, dout, batch, f, d, self, dx, s); return true;
+    default: return false;
   }
+}
+
+static bool launch_dot_bwd_dense(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                 int self, float *dx, hipStream_t s) {
+  switch (r.nfb) {
+    case 1: return launch_dot_bwd_dense_e<1>(r, x, dout, batch, f, d, self, dx, s);
+    case 2: return launch_dot_bwd_dense_e<2>(r, x, dout, batch, f, d, self, dx, s);
+    case 4: return launch_dot_bwd_dense_e<4>(r, x, dout, batch, f, d, self, dx, s);
+    default: return false;
+  }
+}
+
+template <int DP, int NB>
+static bool launch_dot_bwd_mfma_nb(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                   int self, float *dx, hipStream_t s) {
+  (void)ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_interaction_bwd_mfma_kernel<DP, NB>), (int)r.lds_limit);
+  hipLaunchKernelGGL((dot_interaction_bwd_mfma_kernel<DP, NB>), dim3((unsigned)r.grid), dim3((unsigned)r.threads),
+                     (size_t)r.lds, s, x, dout, batch, f, d, self, dx);
+  return true;
+}
+
+template <int DP>
+static bool launch_dot_bwd_mfma_dp(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                   int self, float *dx, hipStream_t s) {
+  switch (r.nb) {
+    case 1: return launch_dot_bwd_mfma_nb<DP, 1>(r, x, dout, batch, f, d, self, dx, s);
+    case 2: return launch_dot_bwd_mfma_nb<DP, 2>(r, x, dout, batch, f, d, self, dx, s);
+    case 3: return launch_dot_bwd_mfma_nb<DP, 3>(r, x, dout, batch, f, d, self, dx, s);
+    case 4: return launch_dot_bwd_mfma_nb<DP, 4>(r, x, dout, batch, f, d, self, dx, s);
+    default: return false;
+  }
+}
+
+static bool launch_dot_bwd_mfma(const DotRoute &r, const float *x, const float *dout, int64_t batch, int f, int d,
+                                int self, float *dx, hipStream_t s) {
+  switch (r.dp) {
+    case 8: return launch_dot_bwd_mfma_dp<8>(r, x, dout, batch, f, d, self, dx, s);
+    case 16: return launch_dot_bwd_mfma_dp<16>(r, x, dout, batch, f, d, self, dx, s);
+    case 32: return launch_dot_bwd_mfma_dp<32>(r, x, dout, batch, f, d, self, dx, s);
+    case 64: return launch_dot_bwd_mfma_dp<64>(r, x, dout, batch, f, d, self, dx, s);
+    case 128: return launch_dot_bwd_mfma_dp<128>(r, x, dout, batch, f, d, self, dx, s);
+    default: return false;
+  }
+}
+
+static bool launch_dot_mfma(const DotRoute &r, const float *x, int64_t batch, int f, int d, int self, int skip,
+                            float *out, hipStream_t s, int64_t out_stride) {
+  switch (r.dp) {
+    case 8: return launch_dot_mfma_dp<8>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 16: return launch_dot_mfma_dp<16>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 32: return launch_dot_mfma_dp<32>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 64: return launch_dot_mfma_dp<64>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    case 128: return launch_dot_mfma_dp<128>(r, x, batch, f, d, self, skip, out, s, out_stride);
+    default: return false;
+  }
+}
+
+// One forward / backward call of either entry-point pair.  `stride` is the row stride of the packed pairs
+// (the strided entries only).  A refused shape launches nothing.
+static int run_dot_fwd(const char *who, const float *x, int64_t batch, int f, int d, int self, int skip, float *out,
+                       int strided, int64_t stride, hipStream_t s) {
+  const DotRoute r = dot_decide_fwd(batch, f, d, self, skip, strided, dot_switches());
+  if (r.kernel == kDotNone) return TFRS_OK;   // no pairs: the output is empty
+  if (r.kernel == kDotRefused) {
+    if (strided) set_error("%s: %d features x %d dims are not covered by the strided kernel", who, f, d);
+    else set_error("%s: %d features x %d dims do not fit the LDS staging", who, f, d);
+    return TFRS_ENOTIMPL;
+  }
+  TFRS_CHECK_ARG(x && out, "%s: NULL pointer", who);
+  if (r.kernel == kDotGather) {
+    hipLaunchKernelGGL(dot_interaction_fwd_kernel, dim3((unsigned)r.grid), dim3((unsigned)r.threads), (size_t)r.lds, s, x,
+                       batch, f, d, self, skip, out);
+  } else if (!launch_dot_mfma(r, x, batch, f, d, self, skip, out, s, strided ? stride : (int64_t)dot_pairs(f, self))) {
+    set_error("%s: no kernel for route %d at %d features x %d dims", who, r.kernel, f, d);
+    return TFRS_ENOTIMPL;
+  }
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+static int run_dot_bwd(const char *who, const float *x, const float *dout, int64_t batch, int f, int d, int self,
+                       int skip, float *dx, int strided, int64_t stride, hipStream_t s) {
+  const DotRoute r = dot_decide_bwd(batch, f, d, self, skip, strided, dot_switches());
+  if (r.kernel == kDotRefused) {
+    if (strided) set_error("%s: %d features x %d dims are not covered by the strided kernel", who, f, d);
+    else set_error("%s: %d features x %d dims do not fit the LDS staging", who, f, d);
+    return TFRS_ENOTIMPL;
+  }
+  if (r.kernel == kDotNone) {   // no pairs: the input has no influence on the (empty) output
+    TFRS_CHECK_ARG(dx, "%s: NULL pointer", who);
+    TFRS_HIP(hipMemsetAsync(dx, 0, (size_t)batch * f * d * sizeof(float), s));
+    return TFRS_OK;
+  }
+  TFRS_CHECK_ARG(x && dout && dx, "%s: NULL pointer", who);
+  const int64_t st = strided ? stride : (int64_t)dot_pairs(f, self);
+  bool ok = true;
+  switch (r.kernel) {
+    case kDotBwdH16: ok = launch_dot_bwd_h16(r, x, dout, batch, f, self, dx, s, st); break;
+    case kDotBwdPc: ok = launch_dot_bwd_pc(r, x, dout, batch, f, d, self, dx, s, st); break;
+    case kDotBwdDense: ok = launch_dot_bwd_dense(r, x, dout, batch, f, d, self, dx, s); break;
+    case kDotBwdMfma: ok = launch_dot_bwd_mfma(r, x, dout, batch, f, d, self, dx, s); break;
+    case kDotGather:
+      hipLaunchKernelGGL(dot_interaction_bwd_kernel, dim3((unsigned)r.grid), dim3((unsigned)r.threads), (size_t)r.lds, s,
+                         x, dout, batch, f, d, self, skip, dx);
+      break;
+    default: ok = false;
+  }
+  if (!ok) {
+    set_error("%s: no kernel for route %d at %d features x %d dims", who, r.kernel, f, d);
+    return TFRS_ENOTIMPL;
+  }
+  TFRS_LAUNCH_CHECK();
+  return TFRS_OK;
+}
+
+// out: int64[32], the forward route in [0..15], the backward route in [16..31] (tfrs_hip.h)
+static void dot_route_report(const DotRoute &r, int64_t *o) {
+  const int64_t v[16] = {r.kernel, r.dp, r.nb, r.stage, r.blocks, r.nfb, r.maxe, r.nstep, r.ney, r.nset,
+                         r.grid, r.threads, r.lds, r.lds_limit, r.kh, r.aux};
+  for (int i = 0; i < 16; ++i) o[i] = v[i];
+}
+
+static void dot_plan(int64_t batch, int f, int d, int self, int skip, int strided, const DotSwitches &sw, int64_t *out) {
+  dot_route_report(dot_decide_fwd(batch, f, d, self, skip, strided, sw), out);
+  dot_route_report(dot_decide_bwd(batch, f, d, self, skip, strided, sw), out + 16);
 }
 
 }  // namespace tfrs
@@ -2458,25 +2696,36 @@ extern "C" int tfrs_cross_bwd_f16_saved_acc(const float *x0, const float *x, con
                           workspace, (hipStream_t)stream, u, dx0_add, add_dx);
 }
 
+// ---- what the DotInteraction launchers would choose at a shape (host only; see tfrs_hip.h) ------
+extern "C" int tfrs_dot_interaction_plan(int64_t batch, int f, int d, int self_interaction, int skip_gather,
+                                         int strided, int64_t *out) {
+  TFRS_CHECK_ARG(out != nullptr, "dot_interaction_plan: NULL pointer");
+  TFRS_CHECK_ARG(batch >= 1 && f >= 1 && d >= 1, "dot_interaction_plan: bad shape");
+  TFRS_CHECK_ARG(!(strided && skip_gather), "dot_interaction_plan: the strided entries have no skip_gather");
+  dot_plan(batch, f, d, self_interaction != 0, skip_gather != 0, strided != 0, dot_switches(), out);
+  return TFRS_OK;
+}
+
+// n shapes at once, (batch, f, d, self_interaction, skip_gather, strided) each, under one reading of the switches
+extern "C" int tfrs_dot_interaction_plan_many(int64_t n, const int64_t *shapes, int64_t *out) {
+  TFRS_CHECK_ARG(n >= 0 && (n == 0 || (shapes != nullptr && out != nullptr)), "dot_interaction_plan_many: NULL pointer");
+  const DotSwitches sw = dot_switches();
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t *a = shapes + 6 * i;
+    TFRS_CHECK_ARG(a[0] >= 1 && a[1] >= 1 && a[2] >= 1 && a[1] <= 0x7FFF && a[2] <= 0x7FFF && !(a[5] && a[4]),
+                   "dot_interaction_plan_many: bad shape at %lld", (long long)i);
+    dot_plan(a[0], (int)a[1], (int)a[2], a[3] != 0, a[4] != 0, a[5] != 0, sw, out + 32 * i);
+  }
+  return TFRS_OK;
+}
+
 extern "C" int tfrs_dot_interaction_fwd(const float *x, int64_t batch, int f, int d,
                                         int self_interaction, int skip_gather, float *out,
                                         void *stream) {
   TFRS_CHECK_ARG(batch >= 0 && f >= 1 && d >= 1, "dot_interaction_fwd: bad shape");
   if (batch == 0) return TFRS_OK;
-  TFRS_CHECK_ARG(x && out, "dot_interaction_fwd: NULL pointer");
-  if (launch_dot_mfma(x, batch, f, d, self_interaction, skip_gather, out, (hipStream_t)stream)) {
-    TFRS_LAUNCH_CHECK();
-    return TFRS_OK;
-  }
-  const size_t lds = (size_t)4 * f * (d + 1) * sizeof(float);
-  if (lds > 64 * 1024) {
-    set_error("dot_interaction_fwd: %d features x %d dims do not fit the LDS staging", f, d);
-    return TFRS_ENOTIMPL;
-  }
-  hipLaunchKernelGGL(dot_interaction_fwd_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), lds,
-                     (hipStream_t)stream, x, batch, f, d, self_interaction, skip_gather, out);
-  TFRS_LAUNCH_CHECK();
-  return TFRS_OK;
+  return run_dot_fwd("dot_interaction_fwd", x, batch, f, d, self_interaction != 0, skip_gather != 0, out, 0, 0,
+                     (hipStream_t)stream);
 }
 
 // Row-strided variants: the packed pairs are row b of a WIDER matrix (out + b * out_stride), so
@@ -2489,54 +2738,31 @@ extern "C" int tfrs_dot_interaction_fwd_strided(const float *x, int64_t batch, i
                                                 int self_interaction, float *out, int64_t out_stride,
                                                 void *stream) {
   TFRS_CHECK_ARG(batch >= 0 && f >= 1 && d >= 1, "dot_interaction_fwd_strided: bad shape");
-  const int out_dim = self_interaction ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  TFRS_CHECK_ARG(out_stride >= out_dim, "dot_interaction_fwd_strided: out_stride < pairs per sample");
+  TFRS_CHECK_ARG(out_stride >= dot_pairs(f, self_interaction != 0), "dot_interaction_fwd_strided: out_stride < pairs per sample");
   if (batch == 0) return TFRS_OK;
-  TFRS_CHECK_ARG(x && out, "dot_interaction_fwd_strided: NULL pointer");
-  if (launch_dot_mfma(x, batch, f, d, self_interaction, 0, out, (hipStream_t)stream, out_stride)) {
-    TFRS_LAUNCH_CHECK();
-    return TFRS_OK;
-  }
-  set_error("dot_interaction_fwd_strided: %d features x %d dims are not covered by the strided kernel", f, d);
-  return TFRS_ENOTIMPL;
+  return run_dot_fwd("dot_interaction_fwd_strided", x, batch, f, d, self_interaction != 0, 0, out, 1, out_stride,
+                     (hipStream_t)stream);
 }
 
 // 1 when BOTH strided entry points cover the shape (the host class asks before choosing the fused
-// concat path: the forward must not succeed where the backward would refuse).  Mirrors the
-// conditions of launch_dot_mfma_nb (direct-store kernel) and launch_dot_bwd_dense (producer /
-// consumer kernel) including the measurement switches, which route to kernels without a row stride.
+// concat path: the forward must not succeed where the backward would refuse): a query of the
+// launchers' own decision, measurement switches included.
 extern "C" int tfrs_dot_interaction_strided_supported(int64_t batch, int f, int d, int self_interaction) {
-  if (batch < 512 || f < 1 || d < 1 || f > 128 || d > 32 || d % 16 != 0) return 0;
-  const int out_dim = self_interaction ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  // forward: split-fp16 direct-store kernel
-  const int dp = d <= 16 ? 16 : 32, nb = (f + 31) / 32;
-  if (nb > 4 || nb * (dp / 2) > 96) return 0;
-  if ((size_t)(((out_dim + 3) & ~3) + 64) * sizeof(float) > 64 * 1024) return 0;
-  const char *sv = option("TFRS_DOT_STAGE"), *fv = option("TFRS_DOT_FWD"), *dv = option("TFRS_DOT_BWD");
-  if ((sv && sv[0] == '0') || (fv && (fv[0] == 'f' || fv[0] == 's')) || (dv && (dv[0] == 'd' || dv[0] == 'g'))) return 0;
-  // backward: producer / consumer kernel
-  int kh = (f + 7) / 8 * 4;
-  if (((2 * kh + 4) / 4) % 2 == 0) kh += 4;
-  const size_t lds = ((size_t)f * (2 * kh + 4) + 256) * sizeof(float);
-  if (lds > 64 * 1024 || (size_t)f * (2 * kh + 4) + 256 > 0xFFFFu) return 0;
-  const size_t lds_pc = 2 * lds + (size_t)2 * (2 * kh * 32) * sizeof(float);
-  return lds_pc <= 160 * 1024 ? 1 : 0;
+  if (batch < 1 || f < 1 || d < 1) return 0;
+  const DotSwitches sw = dot_switches();
+  const int fwd = dot_decide_fwd(batch, f, d, self_interaction != 0, 0, 1, sw).kernel;
+  const int bwd = dot_decide_bwd(batch, f, d, self_interaction != 0, 0, 1, sw).kernel;
+  return fwd != kDotRefused && bwd != kDotRefused;
 }
 
 extern "C" int tfrs_dot_interaction_bwd_strided(const float *x, const float *dout, int64_t dout_stride,
                                                 int64_t batch, int f, int d, int self_interaction,
                                                 float *dx, void *stream) {
   TFRS_CHECK_ARG(batch >= 0 && f >= 1 && d >= 1, "dot_interaction_bwd_strided: bad shape");
-  const int out_dim = self_interaction ? f * (f + 1) / 2 : f * (f - 1) / 2;
-  TFRS_CHECK_ARG(dout_stride >= out_dim, "dot_interaction_bwd_strided: dout_stride < pairs per sample");
+  TFRS_CHECK_ARG(dout_stride >= dot_pairs(f, self_interaction != 0), "dot_interaction_bwd_strided: dout_stride < pairs per sample");
   if (batch == 0) return TFRS_OK;
-  TFRS_CHECK_ARG(x && dout && dx, "dot_interaction_bwd_strided: NULL pointer");
-  if (launch_dot_bwd_dense(x, dout, batch, f, d, self_interaction, dx, (hipStream_t)stream, dout_stride)) {
-    TFRS_LAUNCH_CHECK();
-    return TFRS_OK;
-  }
-  set_error("dot_interaction_bwd_strided: %d features x %d dims are not covered by the strided kernel", f, d);
-  return TFRS_ENOTIMPL;
+  return run_dot_bwd("dot_interaction_bwd_strided", x, dout, batch, f, d, self_interaction != 0, 0, dx, 1, dout_stride,
+                     (hipStream_t)stream);
 }
 
 extern "C" int tfrs_dot_interaction_bwd(const float *x, const float *dout, int64_t batch, int f,
@@ -2544,27 +2770,6 @@ extern "C" int tfrs_dot_interaction_bwd(const float *x, const float *dout, int64
                                         void *stream) {
   TFRS_CHECK_ARG(batch >= 0 && f >= 1 && d >= 1, "dot_interaction_bwd: bad shape");
   if (batch == 0) return TFRS_OK;
-  TFRS_CHECK_ARG(x && dout && dx, "dot_interaction_bwd: NULL pointer");
-  // TFRS_DOT_BWD=gather selects the second-generation kernel (A operand gathered per element)
-  const char *dv = option("TFRS_DOT_BWD");
-  const bool dense_ok = !(dv && dv[0] == 'g');
-  if (!skip_gather && dense_ok &&
-      launch_dot_bwd_dense(x, dout, batch, f, d, self_interaction, dx, (hipStream_t)stream)) {
-    TFRS_LAUNCH_CHECK();
-    return TFRS_OK;
-  }
-  if (!skip_gather &&
-      launch_dot_bwd_mfma(x, dout, batch, f, d, self_interaction, dx, (hipStream_t)stream)) {
-    TFRS_LAUNCH_CHECK();
-    return TFRS_OK;
-  }
-  const size_t lds = (size_t)4 * f * d * sizeof(float);
-  if (lds > 64 * 1024) {
-    set_error("dot_interaction_bwd: %d features x %d dims do not fit the LDS staging", f, d);
-    return TFRS_ENOTIMPL;
-  }
-  hipLaunchKernelGGL(dot_interaction_bwd_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), lds,
-                     (hipStream_t)stream, x, dout, batch, f, d, self_interaction, skip_gather, dx);
-  TFRS_LAUNCH_CHECK();
-  return TFRS_OK;
+  return run_dot_bwd("dot_interaction_bwd", x, dout, batch, f, d, self_interaction != 0, skip_gather != 0, dx, 0, 0,
+                     (hipStream_t)stream);
 }
