@@ -618,6 +618,50 @@ int tfrs_fingerprint_bytes(const unsigned char *bytes, const int64_t *offsets, i
                            void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * tf.keras.layers.TextVectorization (the title tower of the reference's retrieval tutorials): packed strings
+ * -> token indices in one launch.  Strings are packed as in tfrs_hash_bucket_strong_bytes:
+ * bytes[n_bytes] and offsets[n + 1].  Byte rules, ASCII only:
+ *   standardize  bit TFRS_TEXT_LOWER: A-Z -> a-z; bit TFRS_TEXT_STRIP_PUNCTUATION: the 32 bytes
+ *                !"#$%&'()*+,-./:;<=>?@[\]^_`{|}~ are deleted.  Bytes 0x80-0xFF pass unchanged.
+ *   split        TFRS_TEXT_SPLIT_WHITESPACE: tokens are maximal runs of bytes other than space \t \n \v \f \r
+ *                (a run whose bytes were all deleted is no token); TFRS_TEXT_SPLIT_NONE: the standardised
+ *                string is one token, none when it is empty.
+ * A token is known by the SipHash-2-4 fingerprint of its standardised bytes (the key of tfrs_fingerprint_bytes)
+ * and looked up in a table of tfrs_vocab_build with the probe of tfrs_vocab_lookup (its empty_value rule
+ * included).  Every lane clamps its offsets into [0, n_bytes] and to lo <= hi, and no byte outside [0, n_bytes)
+ * is ever read: malformed offsets give wrong indices, never a read out of bounds.  No synchronisation, no
+ * allocation: capturable.  Bad arguments (NULL pointers, negative counts, a capacity that is no power of two
+ * >= 2 * n_tokens, seq_len < 1 on the dense route) return TFRS_EINVAL before any launch.
+ *
+ * tfrs_text_count_tokens: counts[i] = tokens of string i.
+ * tfrs_text_vectorize: token t of string i -> 2 + value, or 1 when unknown (0 is the padding index).
+ *   row_splits == NULL: dense out[n, seq_len], the first seq_len tokens of a row, zero-filled past the last;
+ *   otherwise ragged out[row_splits[i] + t] for t < row_splits[i + 1] - row_splits[i] (row_splits: the
+ *   exclusive scan of tfrs_text_count_tokens with the same standardize / split).
+ * tfrs_text_token_spans: the ragged emit of adapt: per token its fingerprint and the span [start, end) of its
+ *   RAW bytes in the blob (whitespace split: the maximal run of bytes that are no whitespace; no split: the
+ *   whole string).
+ * The kernel streams a workgroup's strings through an LDS window of TFRS_TEXT_WINDOW_BYTES or reads them
+ * directly (TFRS_TEXT_VARIANT = window / direct), on at most TFRS_TEXT_MAX_BLOCKS workgroups
+ * of 256 strings, grid-stride beyond.
+ * ------------------------------------------------------------------------- */
+#define TFRS_TEXT_LOWER 1
+#define TFRS_TEXT_STRIP_PUNCTUATION 2
+#define TFRS_TEXT_SPLIT_NONE 0
+#define TFRS_TEXT_SPLIT_WHITESPACE 1
+#define TFRS_TEXT_WINDOW_BYTES 16384
+#define TFRS_TEXT_MAX_BLOCKS 2048
+int tfrs_text_count_tokens(const unsigned char *bytes, int64_t n_bytes, const int64_t *offsets, int64_t n,
+                           int standardize, int split, int64_t *counts, void *stream);
+int tfrs_text_vectorize(const unsigned char *bytes, int64_t n_bytes, const int64_t *offsets, int64_t n,
+                        int standardize, int split, const void *table, int64_t capacity, int64_t n_tokens,
+                        int64_t empty_value, const int64_t *row_splits, int64_t seq_len, int64_t *out,
+                        void *stream);
+int tfrs_text_token_spans(const unsigned char *bytes, int64_t n_bytes, const int64_t *offsets, int64_t n,
+                          int standardize, int split, const int64_t *row_splits, int64_t *fingerprints,
+                          int64_t *starts, int64_t *ends, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Retrieval.call loss (tasks/retrieval.py:172-210, layers/loss.py:114-158):
  * in-batch sampled softmax without materialising the [nq, nc] logits.
  *   S = q c^T [/ temperature] [- log clip(p_c, 1e-6, 1)]

@@ -84,6 +84,9 @@ SIGNATURES = {
     "tfrs_vocab_lookup": (c_int, [P, c_int, c_i64, P, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_int,
                                   P, P, P]),
     "tfrs_fingerprint_bytes": (c_int, [P, P, c_i64, P, P]),
+    "tfrs_text_count_tokens": (c_int, [P, c_i64, P, c_i64, c_int, c_int, P, P]),
+    "tfrs_text_vectorize": (c_int, [P, c_i64, P, c_i64, c_int, c_int, P, c_i64, c_i64, c_i64, P, c_i64, P, P]),
+    "tfrs_text_token_spans": (c_int, [P, c_i64, P, c_i64, c_int, c_int, P, P, P, P, P]),
     "tfrs_embedding_scatter_add_bwd": (c_int, [P, P, P, c_i64, c_int, P, P, c_float, c_float,
                                                c_int, P]),
     "tfrs_embedding_scatter_add_workspace_bytes": (c_size_t, [c_i64]),

@@ -39,6 +39,7 @@ SOURCES = [
     "shard_route.hip",
     "hashing.hip",
     "vocab.hip",
+    "text.hip",
     "softmax.hip",
     "softmax16.hip",
     "softmax_mined.hip",

@@ -12,38 +12,9 @@
 // nothing but the id and the bucket ever touches memory.  Strings arrive as one packed byte
 // buffer + offsets[n + 1]; a lane walks its own string 8 bytes at a time.
 #include "common.h"
+#include "siphash.h"
 
 namespace tfrs {
-
-struct Sip {
-  uint64_t v0, v1, v2, v3;
-  __device__ __forceinline__ Sip(uint64_t k0, uint64_t k1)
-      : v0(k0 ^ 0x736f6d6570736575ull), v1(k1 ^ 0x646f72616e646f6dull),
-        v2(k0 ^ 0x6c7967656e657261ull), v3(k1 ^ 0x7465646279746573ull) {}
-  static __device__ __forceinline__ uint64_t rotl(uint64_t x, int b) {
-    return (x << b) | (x >> (64 - b));
-  }
-  __device__ __forceinline__ void round() {
-    v0 += v1; v1 = rotl(v1, 13) ^ v0; v0 = rotl(v0, 32);
-    v2 += v3; v3 = rotl(v3, 16) ^ v2;
-    v0 += v3; v3 = rotl(v3, 21) ^ v0;
-    v2 += v1; v1 = rotl(v1, 17) ^ v2; v2 = rotl(v2, 32);
-  }
-  __device__ __forceinline__ void absorb(uint64_t m) {
-    v3 ^= m;
-    round();
-    round();
-    v0 ^= m;
-  }
-  __device__ __forceinline__ uint64_t finish() {
-    v2 ^= 0xff;
-    round();
-    round();
-    round();
-    round();
-    return v0 ^ v1 ^ v2 ^ v3;
-  }
-};
 
 // h mod m by Barrett reduction with the host-computed recip = floor((2^64 - 1) / m): the
 // estimate q = mulhi(h, recip) is never above and at most 2 below floor(h / m), so two
@@ -127,10 +98,7 @@ __global__ void __launch_bounds__(256) hash_bytes_kernel(const unsigned char *__
                                   num_bins, recip);
 }
 
-// The full 64-bit SipHash-2-4 of every packed string under ONE fixed key (the SipHash paper's test key
-// 00 01 .. 0f): the keys of StringLookup's vocabulary table (vocab.hip).
-constexpr uint64_t kFingerprintK0 = 0x0706050403020100ull, kFingerprintK1 = 0x0f0e0d0c0b0a0908ull;
-
+// tfrs_fingerprint_bytes: the keys of StringLookup's vocabulary table (the fixed key is in siphash.h)
 __global__ void __launch_bounds__(256) fingerprint_bytes_kernel(const unsigned char *__restrict__ bytes,
                                                                 const int64_t *__restrict__ offsets,
                                                                 int64_t n, int64_t *__restrict__ out) {

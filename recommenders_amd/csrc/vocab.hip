@@ -15,23 +15,11 @@
 // EVERY probe loop stops after `capacity` steps, whatever the table holds: a malformed table gives wrong
 // indices, never a kernel that spins.
 #include "common.h"
+#include "vocab_probe.h"
 
 namespace tfrs {
 
-constexpr int64_t kVocabEmpty = TFRS_VOCAB_EMPTY_KEY;
 constexpr int kVocabMaxBlocks = 2048;   // grid cap: 256 CUs x 8 blocks of 256 lanes, grid-stride beyond
-
-typedef long long vocab_slot_t __attribute__((ext_vector_type(2)));   // .x = key, .y = value
-
-// the 64-bit finalizer of MurmurHash3 (Appleby, public domain): every input bit reaches every output bit
-__host__ __device__ __forceinline__ uint64_t vocab_mix(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 
 __global__ void __launch_bounds__(256) vocab_clear_kernel(vocab_slot_t *__restrict__ table, int64_t capacity,
                                                           uint32_t *__restrict__ flags) {
@@ -79,7 +67,6 @@ __global__ void __launch_bounds__(256) vocab_lookup_kernel(
     const IdT *__restrict__ ids, int64_t n, const vocab_slot_t *__restrict__ table, int64_t capacity,
     int64_t base, int has_mask, int64_t mask_key, int64_t empty_value, int64_t oov_base, int64_t num_oov,
     int oov_unsigned, unsigned long long *__restrict__ unknown, int64_t *__restrict__ out) {
-  const uint64_t mask = (uint64_t)capacity - 1;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t key = (int64_t)ids[i];
@@ -87,20 +74,7 @@ __global__ void __launch_bounds__(256) vocab_lookup_kernel(
       out[i] = 0;
       continue;
     }
-    int64_t value = -1;
-    if (key == kVocabEmpty) {
-      value = empty_value;
-    } else {
-      uint64_t slot = vocab_mix((uint64_t)key) & mask;
-      for (int64_t step = 0; step < capacity; ++step, slot = (slot + 1) & mask) {
-        const vocab_slot_t s = table[slot];
-        if (s.x == key) {
-          value = s.y;
-          break;
-        }
-        if (s.x == kVocabEmpty) break;
-      }
-    }
+    const int64_t value = vocab_probe(table, capacity, key, empty_value);
     int64_t index;
     if (value >= 0) {
       index = base + value;

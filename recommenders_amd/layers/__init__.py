@@ -2,4 +2,5 @@
 
 from recommenders_amd.layers import blocks, embedding, sharded_embedding, factorized_top_k, feature_interaction, loss  # noqa: F401
 from recommenders_amd.layers import feature_multiplexing, hashing, preprocessing  # noqa: F401
-from recommenders_amd.layers.preprocessing import IntegerLookup, StringLookup  # noqa: F401
+from recommenders_amd.layers.hashing import PackedStrings  # noqa: F401
+from recommenders_amd.layers.preprocessing import IntegerLookup, StringLookup, TextVectorization  # noqa: F401

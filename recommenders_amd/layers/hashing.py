@@ -10,6 +10,9 @@ offsets and hashed by ``tfrs_hash_bucket_strong_bytes``.  Output: int64 buckets 
 input's shape on the GPU (ragged inputs keep their row splits).
 
 The unsalted Keras mode (FarmHash64) is not used on this path and raises.
+
+``PackedStrings`` is that packed form as an input type of its own: text that already lies in HBM is read there by
+``TextVectorization`` and ``StringLookup`` (``layers/preprocessing.py``) without a host pass.
 """
 
 from typing import Optional, Sequence, Union
@@ -31,15 +34,82 @@ def _device(device: Optional[torch.device]) -> torch.device:
   return torch.device("cuda")
 
 
-def pack_strings(arr: np.ndarray, dev: torch.device):
-  """Strings (str -> UTF-8, or bytes) of any shape -> (byte blob, offsets[n + 1]) on ``dev``."""
+def _pack_host(arr):
+  """Strings (str -> UTF-8, or bytes) of any shape -> (uint8 blob, int64 offsets[n + 1]) as NumPy arrays."""
   flat = np.asarray(arr).reshape(-1)
   enc = [x if isinstance(x, (bytes, np.bytes_)) else str(x).encode("utf-8") for x in flat]
   offsets = np.zeros(len(enc) + 1, dtype=np.int64)
   np.cumsum([len(e) for e in enc], out=offsets[1:])
-  blob = (np.frombuffer(b"".join(enc), dtype=np.uint8).copy() if offsets[-1]
-          else np.zeros(1, dtype=np.uint8))
+  return np.frombuffer(b"".join(enc), dtype=np.uint8).copy(), offsets
+
+
+def pack_strings(arr: np.ndarray, dev: torch.device):
+  """Strings (str -> UTF-8, or bytes) of any shape -> (byte blob, offsets[n + 1]) on ``dev``."""
+  blob, offsets = _pack_host(arr)
+  if not blob.size:
+    blob = np.zeros(1, dtype=np.uint8)
   return torch.from_numpy(blob).to(dev), torch.from_numpy(offsets).to(dev)
+
+
+class PackedStrings:
+  """``n`` strings as one ``uint8`` blob and ``int64`` ``offsets[n + 1]``: string ``i`` is
+  ``bytes[offsets[i]:offsets[i + 1]]``.  The form in which text can stay in HBM between calls:
+  ``TextVectorization`` and ``StringLookup`` read it where it lies.
+
+  ``validate=True`` checks that the offsets start at 0, never decrease and end at ``bytes.numel()`` (one host
+  read when the tensors live on the GPU) and raises ``ValueError`` otherwise; pass ``validate=False`` for tensors
+  that are refilled in place under a captured graph."""
+
+  def __init__(self, bytes: torch.Tensor, offsets: torch.Tensor, validate: bool = True):
+    if not (isinstance(bytes, torch.Tensor) and isinstance(offsets, torch.Tensor)):
+      raise ValueError("PackedStrings needs two tensors: uint8 bytes and int64 offsets")
+    if bytes.dtype != torch.uint8 or bytes.ndim != 1:
+      raise ValueError(f"`bytes` must be a uint8 vector; got {bytes.dtype} of shape {tuple(bytes.shape)}")
+    if offsets.dtype != torch.int64 or offsets.ndim != 1 or offsets.numel() < 1:
+      raise ValueError(f"`offsets` must be an int64 vector of length n + 1; got {offsets.dtype} of shape "
+                       f"{tuple(offsets.shape)}")
+    if bytes.device != offsets.device:
+      raise ValueError(f"`bytes` ({bytes.device}) and `offsets` ({offsets.device}) must share a device")
+    if validate:
+      first, last = int(offsets[0]), int(offsets[-1])
+      if first != 0:
+        raise ValueError(f"offsets[0] must be 0; got {first}")
+      if bool((offsets[1:] < offsets[:-1]).any()):
+        raise ValueError("offsets must not decrease")
+      if last != bytes.numel():
+        raise ValueError(f"offsets[-1] must be the byte count {bytes.numel()}; got {last}")
+    self.bytes = bytes.contiguous()
+    self.offsets = offsets.contiguous()
+
+  @classmethod
+  def from_strings(cls, strings, device: Optional[torch.device] = None) -> "PackedStrings":
+    """A list or array of ``str`` (-> UTF-8) or ``bytes``, of any shape, packed in order on ``device``."""
+    dev = _device(device)
+    arr = strings if isinstance(strings, np.ndarray) else np.array(strings, dtype=object)
+    blob, offsets = _pack_host(arr)
+    return cls(torch.from_numpy(blob).to(dev), torch.from_numpy(offsets).to(dev), validate=False)
+
+  @property
+  def n(self) -> int:
+    return self.offsets.numel() - 1
+
+  def __len__(self) -> int:
+    return self.n
+
+  @property
+  def device(self) -> torch.device:
+    return self.bytes.device
+
+  def to(self, device) -> "PackedStrings":
+    device = torch.device(device)
+    if self.bytes.device == device:
+      return self
+    return PackedStrings(self.bytes.to(device), self.offsets.to(device), validate=False)
+
+  def tolist(self) -> list:
+    """The strings as a list of ``bytes`` (a host copy)."""
+    blob, off = self.bytes.cpu().numpy().tobytes(), self.offsets.cpu().tolist()
+    return [blob[a:b] for a, b in zip(off[:-1], off[1:])]
 
 
 class Hashing(torch.nn.Module):

@@ -1,4 +1,5 @@
-"""Vocabulary layers: ``IntegerLookup`` and ``StringLookup`` on a device-resident hash table.
+"""Vocabulary layers: ``IntegerLookup`` and ``StringLookup`` on a device-resident hash table, and
+``TextVectorization`` (at the end of this file), which standardises, splits and looks up text in one kernel.
 
 The reference's tutorials put ``tf.keras.layers.StringLookup(vocabulary=..., mask_token=None)`` or
 ``tf.keras.layers.IntegerLookup(vocabulary=..., mask_value=None)`` in front of every ``Embedding``.  Keras is
@@ -32,7 +33,7 @@ import numpy as np
 import torch
 
 from recommenders_amd import _lib
-from recommenders_amd.layers.hashing import _device, pack_strings
+from recommenders_amd.layers.hashing import PackedStrings, _device, pack_strings
 from recommenders_amd.layers.tpu_embedding_layer import RaggedIds, SparseIds
 
 EMPTY_KEY = -(1 << 63)        # TFRS_VOCAB_EMPTY_KEY: marks a free slot, never stored in the table
@@ -363,6 +364,14 @@ class StringLookup(_IndexLookup):
     return sorted(by_token, key=lambda t: -counts[t])             # stable: count descending
 
   def _lookup(self, inputs, validate: bool) -> torch.Tensor:
+    if isinstance(inputs, PackedStrings):      # each packed string is one token; nothing is packed on the host
+      table = self._require_table()
+      packed = inputs.to(table.device)
+      keys = torch.empty((packed.n,), dtype=torch.int64, device=table.device)
+      blob = packed.bytes if packed.bytes.numel() else packed.bytes.new_zeros(1)
+      _lib.check(_lib.load().tfrs_fingerprint_bytes(_lib.ptr(blob), _lib.ptr(packed.offsets), packed.n,
+                                                    _lib.ptr(keys), _lib.current_stream()))
+      return self._lookup_keys(keys, validate)
     if isinstance(inputs, torch.Tensor):
       raise ValueError(f"StringLookup needs string input; got a tensor of {inputs.dtype}")
     arr = _string_array(inputs)
@@ -382,3 +391,204 @@ class StringLookup(_IndexLookup):
     oov = len(names) - 1
     idx = idx.astype(np.int64)
     return names[np.where((idx >= 0) & (idx < oov), idx, oov)]
+
+
+# ---- TextVectorization -------------------------------------------------------------------------------
+TEXT_WINDOW_BYTES = 16384     # TFRS_TEXT_WINDOW_BYTES: the LDS window of the kernel's window variant
+TEXT_MAX_BLOCKS = 2048        # TFRS_TEXT_MAX_BLOCKS: workgroups of 256 strings per launch, grid-stride beyond
+PUNCTUATION = b"!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"     # the 32 bytes `strip_punctuation` deletes
+WHITESPACE = b" \t\n\v\f\r"                              # the 6 bytes `split="whitespace"` splits at
+_STANDARDIZE = {None: 0, "lower": 1, "strip_punctuation": 2, "lower_and_strip_punctuation": 3}   # TFRS_TEXT_* bits
+_SPLIT = {None: 0, "whitespace": 1}
+_LOWER = bytes.maketrans(bytes(range(65, 91)), bytes(range(97, 123)))
+
+
+def _standardize(text: bytes, mode) -> bytes:
+  """The kernel's standardisation restated on the host, byte by byte, ASCII only (``adapt`` runs it over one
+  span per distinct token)."""
+  code = _STANDARDIZE[mode]
+  if code & 2:
+    text = text.translate(None, PUNCTUATION)
+  if code & 1:
+    text = text.translate(_LOWER)
+  return text
+
+
+def _text_batches(data):
+  if isinstance(data, PackedStrings):
+    return [data]
+  if isinstance(data, (list, tuple)) and any(isinstance(x, PackedStrings) for x in data):
+    return list(data)
+  return _batches(data)
+
+
+class TextVectorization(torch.nn.Module):
+  """``tf.keras.layers.TextVectorization``: strings -> int64 token indices on the GPU, standardised, split and
+  looked up by ONE kernel (``csrc/text.hip``); the first layer of the title tower
+  ``TextVectorization -> Embedding(mask_zero=True) -> GlobalAveragePooling1D`` of the reference's tutorials,
+  whose other half is ``embedding.embedding_lookup_sparse(table, values, row_splits, combiner="mean")``.
+
+  Keras is not part of the reference tree: the rules below are this layer's contract.
+
+  Index 0 is the padding token ``""``, index 1 is ``"[UNK]"``, the vocabulary follows from 2; ``max_tokens`` counts
+  the two special entries.  Standardisation works on bytes and knows ASCII only: ``lower`` maps ``A-Z`` to
+  ``a-z``; ``strip_punctuation`` DELETES the 32 bytes of ``PUNCTUATION`` (``it's`` -> ``its``, ``a-b`` -> ``ab``,
+  ``a - b`` -> ``a``, ``b``); bytes ``0x80-0xFF`` pass unchanged (``É`` is not lowered).  ``split="whitespace"``
+  cuts at the six bytes of ``WHITESPACE``: tokens are maximal runs of other bytes, and a token whose bytes were all
+  deleted does not exist; ``split=None`` makes the whole standardised string one token, and an empty one no token.
+  A token is known by the 64-bit SipHash-2-4 fingerprint of its standardised bytes, as in ``StringLookup``, which
+  holds the vocabulary, the table and the persistent state of this layer.
+
+  Input: a list or array of ``str`` / ``bytes`` of shape ``[n]`` or ``[n, 1]`` (packed on the host per call, as
+  ``StringLookup`` does), or a ``PackedStrings``.  Output, int64 on the GPU:
+
+  * ``output_sequence_length=L``: dense ``[n, L]``, the first ``L`` tokens, padded with 0.  One launch, no host
+    synchronisation, nothing allocated but the output: with a device-resident ``PackedStrings`` the call can be
+    captured in a graph.
+  * ``ragged=True``: a ``RaggedIds`` whose values hold no 0.  One count pass, one host read of the total, one
+    launch.
+  * neither: dense, padded to the longest row of the batch.  This costs one count pass and one host read of the
+    longest row's length before the launch.
+
+  One very long string is walked by one lane of the kernel: correct, and slow for that string alone."""
+
+  def __init__(self, max_tokens: Optional[int] = None, standardize="lower_and_strip_punctuation",
+               split="whitespace", ngrams=None, output_mode: str = "int",
+               output_sequence_length: Optional[int] = None, vocabulary=None, ragged: bool = False,
+               device: Optional[torch.device] = None):
+    super().__init__()
+    if callable(standardize):
+      raise NotImplementedError("a callable `standardize` cannot run inside the kernel; standardise the strings "
+                                "first and pass standardize=None")
+    if standardize not in _STANDARDIZE:
+      raise ValueError(f"`standardize` must be one of {[k for k in _STANDARDIZE]}; got {standardize!r}")
+    if callable(split) or split == "character":
+      raise NotImplementedError(f"split={split!r}: only 'whitespace' and None are on the hot path")
+    if split not in _SPLIT:
+      raise ValueError(f"`split` must be 'whitespace' or None; got {split!r}")
+    if ngrams is not None:
+      raise NotImplementedError("ngrams are not on the hot path")
+    if output_mode != "int":
+      raise NotImplementedError(f"output_mode={output_mode!r}: only 'int' is on the hot path")
+    if ragged and output_sequence_length is not None:
+      raise ValueError("`ragged=True` and `output_sequence_length` exclude each other")
+    if output_sequence_length is not None and int(output_sequence_length) < 1:
+      raise ValueError(f"`output_sequence_length` must be at least 1; got {output_sequence_length}")
+    self.standardize, self.split = standardize, split
+    self.output_mode = output_mode
+    self.output_sequence_length = None if output_sequence_length is None else int(output_sequence_length)
+    self.ragged = bool(ragged)
+    self._device = device
+    self._lookup = StringLookup(max_tokens=max_tokens, num_oov_indices=1, mask_token="", oov_token="[UNK]",
+                                device=device)
+    if vocabulary is not None:
+      self.set_vocabulary(vocabulary)
+
+  @property
+  def max_tokens(self) -> Optional[int]:
+    return self._lookup.max_tokens
+
+  # ---- vocabulary: all of it is the inner StringLookup's ------------------------------------------------
+  def set_vocabulary(self, vocabulary) -> None:
+    """``vocabulary``: a list or array of ``str`` / ``bytes``, taken as they are (NOT standardised); a leading
+    ``["", "[UNK]"]`` is dropped."""
+    self._lookup.set_vocabulary(vocabulary)
+
+  def get_vocabulary(self, include_special_tokens: bool = True) -> List[str]:
+    return self._lookup.get_vocabulary(include_special_tokens)
+
+  def vocabulary_size(self) -> int:
+    return self._lookup.vocabulary_size()
+
+  # ---- launches -----------------------------------------------------------------------------------------
+  def _codes(self):
+    return _STANDARDIZE[self.standardize], _SPLIT[self.split]
+
+  def _pack(self, inputs, dev: torch.device) -> PackedStrings:
+    if isinstance(inputs, PackedStrings):
+      return inputs.to(dev)
+    if isinstance(inputs, torch.Tensor):
+      raise ValueError(f"TextVectorization needs string input; got a tensor of {inputs.dtype}")
+    arr = _string_array(inputs)
+    if arr.dtype.kind not in ("U", "S", "O") or (arr.dtype.kind == "O" and not all(
+        isinstance(x, (str, bytes)) for x in arr.reshape(-1))):
+      raise ValueError(f"TextVectorization needs string input; got dtype {arr.dtype}")
+    if not (arr.ndim == 1 or (arr.ndim == 2 and arr.shape[1] == 1)):
+      raise ValueError(f"TextVectorization needs input of shape [n] or [n, 1]; got {arr.shape}")
+    return PackedStrings.from_strings(arr.reshape(-1), dev)
+
+  def _count(self, packed: PackedStrings):
+    """(tokens per string [n], row_splits [n + 1]) on the device."""
+    standardize, split = self._codes()
+    counts = torch.empty((packed.n,), dtype=torch.int64, device=packed.device)
+    _lib.check(_lib.load().tfrs_text_count_tokens(
+        _lib.ptr(packed.bytes), packed.bytes.numel(), _lib.ptr(packed.offsets), packed.n, standardize, split,
+        _lib.ptr(counts), _lib.current_stream()))
+    row_splits = torch.zeros((packed.n + 1,), dtype=torch.int64, device=packed.device)
+    torch.cumsum(counts, 0, out=row_splits[1:])
+    return counts, row_splits
+
+  def _vectorize(self, packed: PackedStrings, row_splits, seq_len: int, out: torch.Tensor) -> torch.Tensor:
+    standardize, split = self._codes()
+    table = self._lookup._require_table()
+    _lib.check(_lib.load().tfrs_text_vectorize(
+        _lib.ptr(packed.bytes), packed.bytes.numel(), _lib.ptr(packed.offsets), packed.n, standardize, split,
+        _lib.ptr(table), table.shape[0], self._lookup._n_tokens, self._lookup._empty_value, _lib.ptr(row_splits),
+        seq_len, _lib.ptr(out), _lib.current_stream()))
+    return out
+
+  def forward(self, inputs):
+    dev = self._lookup._require_table().device
+    packed = self._pack(inputs, dev)
+    n = packed.n
+    if self.output_sequence_length is not None:
+      out = torch.empty((n, self.output_sequence_length), dtype=torch.int64, device=dev)
+      return self._vectorize(packed, None, self.output_sequence_length, out)
+    counts, row_splits = self._count(packed)
+    if self.ragged:
+      values = torch.empty((int(row_splits[-1]),), dtype=torch.int64, device=dev)
+      if values.numel():
+        self._vectorize(packed, row_splits, 0, values)
+      return RaggedIds(values, row_splits)
+    longest = int(counts.max()) if n else 0
+    out = torch.empty((n, longest), dtype=torch.int64, device=dev)
+    return self._vectorize(packed, None, longest, out) if longest else out
+
+  # ---- adapt ----------------------------------------------------------------------------------------------
+  def _count_batch(self, packed: PackedStrings, totals: collections.Counter) -> None:
+    """Adds the batch's token counts into ``totals``: tokenising, fingerprinting and counting run on the device;
+    the host sees one raw span per distinct fingerprint and standardises it with ``_standardize``."""
+    standardize, split = self._codes()
+    _, row_splits = self._count(packed)
+    total = int(row_splits[-1])
+    if not total:
+      return
+    prints, starts, ends = (torch.empty((total,), dtype=torch.int64, device=packed.device) for _ in range(3))
+    _lib.check(_lib.load().tfrs_text_token_spans(
+        _lib.ptr(packed.bytes), packed.bytes.numel(), _lib.ptr(packed.offsets), packed.n, standardize, split,
+        _lib.ptr(row_splits), _lib.ptr(prints), _lib.ptr(starts), _lib.ptr(ends), _lib.current_stream()))
+    distinct, inverse, counts = torch.unique(prints, return_inverse=True, return_counts=True)
+    first = torch.full((distinct.numel(),), total, dtype=torch.int64, device=packed.device)
+    first.scatter_reduce_(0, inverse, torch.arange(total, device=packed.device), reduce="amin")
+    lo, hi = starts[first], ends[first]
+    lengths = hi - lo
+    at = torch.cumsum(lengths, 0) - lengths          # where each span begins in the gathered bytes
+    which = torch.repeat_interleave(lo - at, lengths) + torch.arange(int(lengths.sum()), device=packed.device)
+    raw = packed.bytes[which].cpu().numpy().tobytes()
+    for a, ln, c in zip(at.tolist(), lengths.tolist(), counts.tolist()):
+      totals[_standardize(raw[a:a + ln], self.standardize)] += c
+
+  def adapt(self, data) -> None:
+    """Builds the vocabulary from data: a list or array of strings, a ``PackedStrings``, or an iterable of such
+    batches.  The data is standardised and split as ``forward`` does; tokens are ordered by count descending,
+    ties by token bytes descending (``StringLookup.adapt``'s rule), and cut to ``max_tokens - 2``."""
+    dev = _device(self._device)
+    totals = collections.Counter()
+    for batch in _text_batches(data):
+      self._count_batch(self._pack(batch, dev), totals)
+    totals.pop(self._lookup.oov_token, None)       # "[UNK]" survives standardize=None: it keeps its own index
+    by_token = sorted(totals, reverse=True)
+    tokens = sorted(by_token, key=lambda t: -totals[t])
+    if self.max_tokens is not None:
+      tokens = tokens[:max(self.max_tokens - 2, 0)]
+    self.set_vocabulary(tokens)
