@@ -107,8 +107,15 @@ int tfrs_index_reserve(tfrs_index_t *index, int64_t capacity, int d, void *strea
 int tfrs_index_append(tfrs_index_t *index, const float *block, int64_t nb, void *stream);
 /* Non-finite inputs (the reference's tf.math.top_k, layers/factorized_top_k.py:605, tolerates NaN / Inf scores; this
  * library's fp16-prefiltered search does NOT: its error bound is built from row norms, and the filter kernels are
- * compiled without NaN semantics).  CONTRACT: candidates and queries must be finite, |x| < 1.8e19 (so that a squared
- * norm stays finite).  Violations are recorded, never silent:
+ * compiled without NaN semantics).  CONTRACT, per candidate row c and per query row q (not per element):
+ *   - every element is finite;
+ *   - the 2-norm is at most 2^120 (1.3e36) -- the norm bounds of the filter then stay finite for every dim up to 128 --
+ *     and every product ||q|| * ||c|| is at most 2^126, so that every score is finite;
+ *   - a row that is not all zero has max |x| >= 2^-120 (7.5e-37): below that the row's power-of-two scale is clamped
+ *     and its fp16 image loses more than the bound accounts for.  (Zero rows are fine.)
+ * Inside these limits the top-K is exact whatever the magnitudes: norms are computed as upper bounds over the whole
+ * range (common.h, norm_upper_bound), never as a sum of squares that under- or overflows.  NaN / Inf are recorded,
+ * never silent:
  *   bit 0 (1)  an indexed candidate row holds NaN / Inf -- set by tfrs_index_set / _append; the host layer raises
  *              ValueError from BruteForce.index / index_from_dataset and drops the index;
  *   bit 1 (2)  a query row of a tfrs_bruteforce_topk[_below] call held NaN / Inf.  Only THAT row of the result is
@@ -196,6 +203,18 @@ int tfrs_debug_topk_plan(int64_t n, int k, int shuffled, int64_t *plan_h);
 int tfrs_debug_fp16_scores(const tfrs_index_t *index, const float *queries, int64_t nq,
                            int64_t row_begin, int64_t row_end, float *out, float *scratch,
                            void *stream);
+/* After the call, scratch[0, nq) holds qk[q] (the query's norm bound times kappa) and scratch[nq, 2 nq) its
+ * power-of-two scale: the query-side inputs of the filter's bound.
+ *
+ * Test hook: the candidate-side inputs of the bound, for stages [stage_begin, stage_end) of the index (a stage is 128
+ * image rows; stage_end <= ceil(rows / 128)).  Plain device-to-device copies on `stream`:
+ *   image_out     the stages' fp16 image rows in image order, 2 * padded_dim16 + 16 bytes each (padded_dim16 = 16, 32,
+ *                 64 or 128: x / scale in natural feature order, zero columns up to padded_dim16, one zero 16-byte slot);
+ *   meta_out      4 floats per stage: {norm, scale, 1 / scale, 0};
+ *   norm_max_out  one float, the largest norm of any stage of the index.
+ * An index of fewer than 65536 rows is not shuffled: image row = candidate row. */
+int tfrs_debug_fp16_image(const tfrs_index_t *index, int64_t stage_begin, int64_t stage_end, void *image_out,
+                          void *meta_out, float *norm_max_out, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Streaming.call (layers/factorized_top_k.py:404-509): one candidate block.

@@ -137,6 +137,21 @@ constexpr float kF16Kappa = 0.0011f;
 constexpr float kF16Tiny = 1.0e-30f;    // absolute slack (f32 subnormal flushes)
 constexpr float kNormSlack = 1.0002f;   // covers the rounding of the f32 norm computation
 
+// The bound holds only while the norms it is built from are UPPER bounds of the true ones.  Every site that computes
+// one holds, for a group of rows of dp features, the largest plain f32 sum of squares `ssq_max` and the largest |x|
+// `amax` of the group.  With amax in [2^-60, 2^60] the row of largest norm R has ||R|| >= amax, its squares neither
+// overflow (dp * 2^120 < 2^128) nor lose more than dp * 2^-150 to underflow (2^-30 dp relative to ||R||^2 >= 2^-120),
+// so sqrt(ssq_max) * kNormSlack is an upper bound within 1e-5 of the slack.  Outside that window squares under- or
+// overflow (below 2^-75 every square is zero), and the bound falls back to ||row|| <= sqrt(dp) * amax: loose by up to
+// sqrt(dp), never too small.  The 2^-149 addend rounds a subnormal product up; FLT_MAX keeps the bound finite, so
+// that qk * norm is never 0 * inf (rows that large are outside the contract of tfrs_hip.h).
+constexpr float kNormWindowLo = 0x1p-60f, kNormWindowHi = 0x1p60f;
+__device__ __forceinline__ float norm_upper_bound(float ssq_max, float amax, int dp) {
+  const float plain = __builtin_sqrtf(ssq_max) * kNormSlack;
+  const float wide = fminf(__builtin_fmaf(amax, __builtin_sqrtf((float)dp) * kNormSlack, 0x1p-149f), __FLT_MAX__);
+  return ((amax > 0.0f && amax < kNormWindowLo) || amax > kNormWindowHi) ? wide : plain;
+}
+
 struct StageMeta {
   float norm;       // max row 2-norm of the stage's rows (rounded up)
   float scale;      // power of two >= max |x| of the stage (1 for an all-zero stage)
@@ -470,7 +485,7 @@ int launch_unpack(const char *packed, int64_t n, int d, const int32_t *rowmap, f
 // filled tail stage is simply rebuilt by the next append).  norm_max: atomicMax on float bits.
 int launch_pack16(const char *packed, int d, int64_t row_begin, int64_t row_end, char *packed16,
                   StageMeta *meta, float *norm_max, hipStream_t stream);
-// qk[q] = ||q||_2 * kNormSlack * kF16Kappa;  qscale[q] = 2^ceil(log2 max|q_d|)
+// qk[q] = norm_upper_bound of ||q||_2 (>= ||q||_2, kNormSlack included) * kF16Kappa;  qscale[q] = 2^ceil(log2 max|q_d|)
 // (also re-arms zero_u32[q] = 0 when given: the per-query overflow counters of the filter pass)
 // (flags: |= kNonfiniteQueries when a query row holds NaN / Inf)
 int launch_query_kappa(const float *q, int64_t nq, int d, float *qk, float *qscale,

@@ -1013,6 +1013,29 @@ extern "C" int tfrs_debug_fp16_scores(const tfrs_index_t *index, const float *qu
   return launch_scan16(a, (hipStream_t)stream);
 }
 
+// Test hook: what the filter's bound is built from -- the fp16 image rows of stages [stage_begin, stage_end) in image
+// order, their StageMeta entries and the index's norm_max.  Device-to-device copies only.
+extern "C" int tfrs_debug_fp16_image(const tfrs_index_t *index, int64_t stage_begin, int64_t stage_end,
+                                     void *image_out, void *meta_out, float *norm_max_out, void *stream) {
+  if (!index || !index->packed16) {
+    set_error("debug_fp16_image: the index has not been built");
+    return TFRS_ESTATE;
+  }
+  TFRS_CHECK_ARG(image_out && meta_out && norm_max_out, "debug_fp16_image: NULL pointer");
+  TFRS_CHECK_ARG(stage_begin >= 0 && stage_end >= stage_begin && stage_end <= padded_rows(index->n) / kTileN,
+                 "debug_fp16_image: bad stage range");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t stage_bytes = (size_t)kTileN * row_bytes16(padded_dim16(index->d));
+  const size_t ns = (size_t)(stage_end - stage_begin);
+  if (ns > 0) {
+    TFRS_HIP(hipMemcpyAsync(image_out, index->packed16 + (size_t)stage_begin * stage_bytes, ns * stage_bytes,
+                            hipMemcpyDeviceToDevice, st));
+    TFRS_HIP(hipMemcpyAsync(meta_out, index->meta + stage_begin, ns * sizeof(StageMeta), hipMemcpyDeviceToDevice, st));
+  }
+  TFRS_HIP(hipMemcpyAsync(norm_max_out, index->norm_max, sizeof(float), hipMemcpyDeviceToDevice, st));
+  return TFRS_OK;
+}
+
 // ----------------------------------------------------------------------------------------
 // Streaming.call, one candidate block
 // ----------------------------------------------------------------------------------------

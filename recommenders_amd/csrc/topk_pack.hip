@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(256) pack16_stage_kernel(const char *__restric
     ssq += __shfl_xor(ssq, 1);
     amax = fmaxf(amax, __shfl_xor(amax, 1));
     if (pl == 0) {
-      s_norm[r] = __builtin_sqrtf(ssq) * kNormSlack;
+      s_norm[r] = ssq;   // (the stage's largest sum of squares becomes its norm below)
       s_amax[r] = amax;
     }
   }
@@ -158,6 +158,7 @@ __global__ void __launch_bounds__(256) pack16_stage_kernel(const char *__restric
     if (tid == 0) {
       const float sc = pow2_ceil(am);
       s_scale = sc;
+      nm = norm_upper_bound(nm, am, dp);
       meta[stage].norm = nm;
       meta[stage].scale = sc;
       meta[stage].inv_scale = 1.0f / sc;
@@ -223,7 +224,7 @@ __global__ void __launch_bounds__(256) pack16_stage_regs_kernel(const char *__re
   ssq += __shfl_xor(ssq, 1);
   amax = fmaxf(amax, __shfl_xor(amax, 1));
   if (pl == 0) {
-    s_norm[r] = __builtin_sqrtf(ssq) * kNormSlack;
+    s_norm[r] = ssq;   // (the stage's largest sum of squares becomes its norm below)
     s_amax[r] = amax;
   }
   __syncthreads();
@@ -237,6 +238,7 @@ __global__ void __launch_bounds__(256) pack16_stage_regs_kernel(const char *__re
     if (tid == 0) {
       const float sc = pow2_ceil(am);
       s_scale = sc;
+      nm = norm_upper_bound(nm, am, DP);
       meta[stage].norm = nm;
       meta[stage].scale = sc;
       meta[stage].inv_scale = 1.0f / sc;
@@ -320,10 +322,14 @@ __global__ void __launch_bounds__(256) query_kappa_kernel(const float *__restric
     amax = fmaxf(amax, __shfl_xor(amax, off));
   }
   if (ok && sub == 0) {
-    // a NaN / Inf element (or a norm beyond the f32 range) makes the sum of squares non-finite: bit 1 of the flag word
-    if (flags && nonfinite_bits(ssq)) atomicOr(flags, kNonfiniteQueries);
+    // a NaN element makes the sum of squares NaN, an Inf element is the row's max |x|: bit 1 of the flag word.  (A sum
+    // that merely overflowed is +Inf: the row is finite and norm_upper_bound does not use the sum.)
+    if (flags && ((__float_as_uint(ssq) & 0x7fffffffu) > 0x7f800000u || nonfinite_bits(amax)))
+      atomicOr(flags, kNonfiniteQueries);
     if (zero_u32) zero_u32[r] = 0u;
-    qk[r] = __builtin_sqrtf(ssq) * kNormSlack * kF16Kappa;
+    // (the 2^-149 addend rounds a subnormal product up; it vanishes in every normal one.  A zero query keeps qk = 0)
+    const float nb = norm_upper_bound(ssq, amax, d);
+    qk[r] = nb > 0.0f ? __builtin_fmaf(nb, kF16Kappa, 0x1p-149f) : 0.0f;
     qscale[r] = pow2_ceil(amax);
   }
 }

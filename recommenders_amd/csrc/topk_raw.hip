@@ -545,7 +545,7 @@ __global__ void __launch_bounds__(NWV * 64) rawscan16_kernel(const RawScanArgs a
       if (off < 32) ss = fmaxf(ss, __shfl_xor(ss, off));
       am = fmaxf(am, __shfl_xor(am, off));
     }
-    const float nrm = __builtin_sqrtf(ss) * kNormSlack;   // (upper bound of the 32 row norms)
+    const float nrm = norm_upper_bound(ss, am, DP);   // (upper bound of the 32 row norms)
     const float cs = pow2_ceil(am);
     const float inv = 1.0f / cs;                          // exact: power of two
     norm_run = fmaxf(norm_run, nrm);
@@ -854,7 +854,7 @@ __global__ void __launch_bounds__(kRawWWaves * 64) rawscan16w_kernel(const RawSc
       am = fmaxf(am, __shfl_xor(am, off));
     }
     }
-    const float nrm = __builtin_sqrtf(nmax) * kNormSlack;   // (upper bound of the 16 row norms)
+    const float nrm = norm_upper_bound(nmax, am, DP);   // (upper bound of the 16 row norms)
     const float cs = pow2_ceil(am);
     const float inv = 1.0f / cs;                            // exact: power of two
     norm_run = fmaxf(norm_run, nrm);
@@ -1105,7 +1105,7 @@ __global__ void __launch_bounds__((CW + 4) * 64) rawscan16pc_kernel(const RawSca
           nmax[gi] = fmaxf(nmax[gi], __shfl_xor(nmax[gi], off));
           am[gi] = fmaxf(am[gi], __shfl_xor(am[gi], off));
         }
-        const float nrm = __builtin_sqrtf(nmax[gi]) * kNormSlack;   // (upper bound of the 16 row norms)
+        const float nrm = norm_upper_bound(nmax[gi], am[gi], DP);   // (upper bound of the 16 row norms)
         const float cs = pow2_ceil(am[gi]);
         inv[gi] = 1.0f / cs;                                        // exact: power of two
         norm_run = fmaxf(norm_run, nrm);
@@ -1400,7 +1400,7 @@ __global__ void __launch_bounds__(256) pack16_raw_kernel(const RawTable *__restr
     const float a_ = fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3]));
     // (the sum of squares of a row is accumulated in a different order than pack16_stage_kernel does:
     // kNormSlack covers the rounding of either; the norm only has to be an upper bound)
-    const float nm = __builtin_sqrtf(n2) * kNormSlack;
+    const float nm = norm_upper_bound(n2, a_, DP);
     const float sc = pow2_ceil(a_);
     s_scale = sc;
     meta[stage].norm = nm;
