@@ -1154,6 +1154,33 @@ int tfrs_scann_search(const float *queries, int64_t nq, int d, const int32_t *pr
                       const int32_t *perm, const float *rows, int64_t p_max, int r, int k, float *out_scores,
                       int32_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * The recurrence of a Keras GRU (reset_after=True, tanh / sigmoid, gates z, r, h) over all `steps` time steps in
+ * ONE launch, and its backward walk in one more (layers/recurrent.py).  The input projection
+ * xproj[batch, steps, 3 units] = x @ kernel + bias[0] and every weight gradient are GEMMs of tfrs_dense_*.
+ *   q = h_{t-1} @ recurrent_kernel[units, 3 units] + recurrent_bias[3 units] (NULL: none)
+ *   z = sigmoid(a_z + q_z), r = sigmoid(a_r + q_r), hh = tanh(a_h + r q_h), h_t = z h_{t-1} + (1 - z) hh
+ * mask[batch, steps] (bytes, NULL: all set): where 0, h_t = h_{t-1}.  h0[batch, units] (NULL: zeros).
+ * go_backwards != 0 walks time indices steps-1 .. 0.  out_seq[batch, steps, units] (optional) is in PROCESSING
+ * order; out_last[batch, units].  The training forward also fills save_z / save_r / save_hh / save_qh / save_hprev
+ * [batch, steps, units], indexed by TIME index (all five or none).
+ *   bwd: dseq (processing order) and dlast are the gradients of out_seq / out_last (each optional);
+ *     da[batch, steps, 3 units] = (da_z, da_r, da_h), the gradient of xproj;
+ *     dg[batch, steps, 3 units] = (da_z, da_r, dq_h): d recurrent_kernel = save_hprev^T @ dg, d recurrent_bias its
+ *     column sums; both by time index, zeros at masked steps; dh0[batch, units].
+ * units <= TFRS_GRU_MAX_UNITS (TFRS_ENOTIMPL above).  batch == 0 or steps == 0 returns without a launch.  No
+ * workspace, no atomics: results are identical from run to run.
+ * ------------------------------------------------------------------------- */
+#define TFRS_GRU_MAX_UNITS 64
+int tfrs_gru_fwd(const float *xproj, const float *recurrent_kernel, const float *recurrent_bias,
+                 const uint8_t *mask, const float *h0, int64_t batch, int steps, int units, int go_backwards,
+                 float *out_seq, float *out_last, float *save_z, float *save_r, float *save_hh, float *save_qh,
+                 float *save_hprev, void *stream);
+int tfrs_gru_bwd(const float *recurrent_kernel, const uint8_t *mask, const float *save_z, const float *save_r,
+                 const float *save_hh, const float *save_qh, const float *save_hprev, const float *dseq,
+                 const float *dlast, int64_t batch, int steps, int units, int go_backwards, float *da, float *dg,
+                 float *dh0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,8 @@ SIGNATURES = {
     "tfrs_scann_search_workspace_bytes": (c_size_t, [c_i64, c_int, c_int, c_int, c_i64, c_int]),
     "tfrs_scann_search": (c_int, [P, c_i64, c_int, P, P, c_int, P, c_int, c_i64, P, c_int, P, c_int, c_int, P, P,
                                   c_i64, c_int, c_int, P, P, P, c_size_t, P]),
+    "tfrs_gru_fwd": (c_int, [P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
+    "tfrs_gru_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

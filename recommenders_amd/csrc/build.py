@@ -48,6 +48,7 @@ SOURCES = [
     "interaction.hip",
     "gemm16.hip",
     "scann.hip",
+    "gru.hip",
 ]
 
 

@@ -195,11 +195,12 @@ class Embedding(torch.nn.Module):
   """``tf.keras.layers.Embedding(input_dim, output_dim)`` on HBM-resident tables."""
 
   def __init__(self, input_dim: int, output_dim: int, validate_ids: bool = False,
-               device: Optional[torch.device] = None):
+               device: Optional[torch.device] = None, mask_zero: bool = False):
     super().__init__()
     self.input_dim = input_dim
     self.output_dim = output_dim
     self.validate_ids = validate_ids
+    self.mask_zero = bool(mask_zero)
     dev = device if device is not None else (
         torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
     w = torch.empty((input_dim, output_dim), dtype=torch.float32, device=dev)
@@ -214,6 +215,15 @@ class Embedding(torch.nn.Module):
     if self.validate_ids:
       return _ValidatedGather.apply(self.embeddings, ids)
     return _GatherFn.apply(self.embeddings, ids)
+
+  def compute_mask(self, ids: torch.Tensor) -> Optional[torch.Tensor]:
+    """Keras' ``Embedding.compute_mask``: ``ids != 0`` with ``mask_zero=True``, else ``None`` (the mask a
+    ``layers.GRU`` takes: ``gru(emb(ids), mask=emb.compute_mask(ids))``)."""
+    if not self.mask_zero:
+      return None
+    if not isinstance(ids, torch.Tensor):
+      ids = torch.as_tensor(ids)
+    return ids != 0
 
 
 class _ValidatedGather(_GatherFn):
