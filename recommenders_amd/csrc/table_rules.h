@@ -118,8 +118,10 @@ struct FtrlRule {
 //     with the same bits).
 //   row scan (a wave per row): lane l owns the features l, l + 64, l + 128, l + 192, ascending, then the same butterfly
 //     over 64 lanes.
-// The two orders differ (by float32 reassociation of non-negative terms only); which route a table takes is a function
-// of (vocab, n, d) alone.
+// The float4 order differs from the row scan's (by float32 reassociation of non-negative terms only); with VEC = 1 a
+// chunk is a feature, lane l owns l, l + 64, ... on both routes and a lane without a feature adds +0, so the two are
+// the same sum (tests/optimizer_handbuilt.py restates both).  Which route a table takes is a function of (vocab, n, d)
+// alone.
 __device__ __forceinline__ float rowwise_sq_add(float partial, float g) {
 #pragma clang fp contract(off)
   return partial + g * g;

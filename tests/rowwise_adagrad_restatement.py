@@ -63,13 +63,18 @@ def _sum_squares(g, order):
   return sq[..., 0]
 
 
-def update(w, acc, g, hp, dtype, order="sequential"):
-  """One step on ``w [r, d]``, ``acc [r]``, ``g [r, d]`` (the summed gradient) in ``dtype`` arithmetic.  Returns a dict:
-  w, acc and the intermediates the bounds need."""
+def update(w, acc, g, hp, dtype, order="sequential", sum_sq=None):
+  """One step on ``w [r, d]``, ``acc [r]``, ``g [r, d]`` (the summed gradient) in ``dtype`` arithmetic.  ``sum_sq``: the
+  rows' ``sum_j g_j * g_j`` taken as given in place of ``order`` -- the kernels' own orders are restated in
+  tests/optimizer_handbuilt.py (``sum_squares_kernel_order``, ``sum_squares_rowscan_order``).  Returns a dict: w, acc and
+  the intermediates the bounds need."""
   t = np.dtype(dtype).type
   w, acc, g = (np.asarray(x, dtype=dtype) for x in (w, acc, g))
   d = g.shape[-1]
-  if dtype == np.float64:
+  if sum_sq is not None:
+    sum_sq = np.asarray(sum_sq)
+    assert sum_sq.dtype == dtype and sum_sq.shape == g.shape[:-1]
+  elif dtype == np.float64:
     sum_sq = (g * g).sum(axis=-1)
   else:
     sum_sq = _sum_squares(g, order)
