@@ -1181,6 +1181,61 @@ int tfrs_gru_bwd(const float *recurrent_kernel, const uint8_t *mask, const float
                  const float *dlast, int64_t batch, int steps, int units, int go_backwards, float *da, float *dg,
                  float *dh0, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Numeric preprocessing (layers/numeric.py; csrc/numeric.hip): the kernels behind Discretization and
+ * Normalization.  Plain pointers, every launch on `stream`, no atomics, no host synchronisation, no allocation.  The
+ * input x is f32, f64, int32 or int64 (TFRS_NUMERIC_*).  Bad arguments (a NULL pointer, a negative count, an unknown
+ * dtype code or mode, a workspace smaller than stated, an input not aligned to its element size) return TFRS_EINVAL
+ * with nothing launched; n == 0 / n_rows == 0 returns TFRS_OK with nothing launched.
+ *
+ * tfrs_bucketize: out[i] = the number of boundaries <= x[i] (std::upper_bound, np.searchsorted(side="right")), as
+ *   TensorFlow's Bucketize kernel computes it: the nb boundaries are f32; f32 input is compared in f32; int32 and
+ *   int64 input is converted to f32 with round-to-nearest-even and compared in f32; f64 input is compared in f64
+ *   against the widened boundaries.  NaN goes to bucket nb; nb == 0 gives zeros; repeated boundaries are legal.  The
+ *   entry does NOT check that the boundaries are sorted (non-decreasing, no NaN): unsorted boundaries give some index
+ *   in [0, nb], never a fault.  Up to TFRS_BUCKETIZE_LDS_BOUNDARIES boundaries each workgroup stages them in LDS;
+ *   beyond, the same branch-free search probes global memory.
+ *
+ * tfrs_normalize: x[n_rows, f] row-major, mean[f], scale[f]; x is converted to f32 first.  f == 1 is one scalar
+ *   statistic over any shape (axis=None).  mode
+ *     TFRS_NORMALIZE_FORWARD          out = (x - mean) / scale   an IEEE subtraction, then an IEEE division
+ *     TFRS_NORMALIZE_INVERT           out = fma(x, scale, mean)
+ *     TFRS_NORMALIZE_BACKWARD         out = x / scale            x is the gradient of the forward's output
+ *     TFRS_NORMALIZE_BACKWARD | TFRS_NORMALIZE_INVERT   out = x * scale   ... of the inverted layer's output
+ *
+ * Moments.  state[f][3] (f64, on the device): per feature the count, the mean and M2, the sum of squared deviations
+ *   from that mean, of everything seen since tfrs_moments_reset (which writes zeros).  tfrs_moments_update folds the
+ *   batch x[n_rows, f] in: the values are converted to f32 (the statistics are those of the f32 values) and
+ *   accumulated in f64 in two launches -- workgroups of TFRS_MOMENTS_SLICE_ELEMENTS / f rows (more once
+ *   TFRS_MOMENTS_MAX_GROUPS workgroups no longer cover the batch) each write one partial per feature into the
+ *   workspace, one workgroup merges them into the state with Chan's pairwise update in an order the shape fixes, so
+ *   the state is bit-identical from run to run.  workspace: tfrs_moments_workspace_bytes(n_rows, f) bytes, 8-byte
+ *   aligned; the size never decreases in either argument, so one workspace sized for the largest batch serves all.
+ *   tfrs_moments_finalize writes f32 mean[f], variance[f] = M2 / count (population) and
+ *   scale[f] = max(sqrt(variance), TFRS_NORMALIZE_EPSILON); a feature with count 0 gets mean 0, variance 1, scale 1
+ *   (Keras' reset values).  Constant data gives variance exactly 0.
+ * ------------------------------------------------------------------------- */
+#define TFRS_NUMERIC_F32 0
+#define TFRS_NUMERIC_F64 1
+#define TFRS_NUMERIC_I32 2
+#define TFRS_NUMERIC_I64 3
+#define TFRS_BUCKETIZE_LDS_BOUNDARIES 4095   /* padded to 4096 f32 = 16 KB of LDS */
+#define TFRS_NORMALIZE_FORWARD 0
+#define TFRS_NORMALIZE_INVERT 1
+#define TFRS_NORMALIZE_BACKWARD 2
+#define TFRS_NORMALIZE_EPSILON 1e-7f         /* Keras backend.epsilon() */
+#define TFRS_MOMENTS_SLICE_ELEMENTS 4096
+#define TFRS_MOMENTS_MAX_GROUPS 1024
+int tfrs_bucketize(const void *x, int dtype, int64_t n, const float *boundaries, int64_t nb, int64_t *out,
+                   void *stream);
+int tfrs_normalize(const void *x, int dtype, int64_t n_rows, int64_t f, const float *mean, const float *scale,
+                   int mode, float *out, void *stream);
+size_t tfrs_moments_workspace_bytes(int64_t n_rows, int64_t f);
+int tfrs_moments_update(const void *x, int dtype, int64_t n_rows, int64_t f, double *state, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int tfrs_moments_finalize(const double *state, int64_t f, float *mean, float *variance, float *scale, void *stream);
+int tfrs_moments_reset(double *state, int64_t f, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

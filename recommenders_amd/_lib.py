@@ -188,6 +188,12 @@ SIGNATURES = {
                                   c_i64, c_int, c_int, P, P, P, c_size_t, P]),
     "tfrs_gru_fwd": (c_int, [P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "tfrs_gru_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P]),
+    "tfrs_bucketize": (c_int, [P, c_int, c_i64, P, c_i64, P, P]),
+    "tfrs_normalize": (c_int, [P, c_int, c_i64, c_i64, P, P, c_int, P, P]),
+    "tfrs_moments_workspace_bytes": (c_size_t, [c_i64, c_i64]),
+    "tfrs_moments_update": (c_int, [P, c_int, c_i64, c_i64, P, P, c_size_t, P]),
+    "tfrs_moments_finalize": (c_int, [P, c_i64, P, P, P, P]),
+    "tfrs_moments_reset": (c_int, [P, c_i64, P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

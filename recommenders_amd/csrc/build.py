@@ -49,6 +49,7 @@ SOURCES = [
     "gemm16.hip",
     "scann.hip",
     "gru.hip",
+    "numeric.hip",
 ]
 
 
@@ -58,7 +59,11 @@ EXTRA_FLAGS = {"topk_scan16.hip": ["-fno-honor-nans"],
                # (the max trees over MFMA accumulators of the block-fed filters: v_max3_f32 without canonicalisation)
                "topk_raw.hip": ["-fno-honor-nans"],
                # MFMA accumulators in VGPRs: the softmax arithmetic reads them directly
-               "softmax16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+               "softmax16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               # Normalization's forward is pinned bit for bit: f32 division and square root correctly rounded (hipcc's
+               # default, stated here so that a changed default cannot change results) and no fused multiply-add formed
+               # from the subtraction and division sequences
+               "numeric.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off"]}
 
 
 def hipcc() -> str:
