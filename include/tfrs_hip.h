@@ -1182,6 +1182,33 @@ int tfrs_gru_bwd(const float *recurrent_kernel, const uint8_t *mask, const float
                  float *dh0, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The recurrence of a Keras LSTM (tanh / sigmoid, gates i, f, c, o, one bias) over all `steps` time steps in ONE
+ * launch, and its backward walk in one more (layers/recurrent.py).  The input projection
+ * xproj[batch, steps, 4 units] = x @ kernel + bias and every weight gradient are GEMMs of tfrs_dense_*.
+ *   p = xproj_t + h_{t-1} @ recurrent_kernel[units, 4 units]
+ *   i = sigmoid(p_i), f = sigmoid(p_f), g = tanh(p_c), o = sigmoid(p_o), c_t = f c_{t-1} + i g, h_t = o tanh(c_t)
+ * mask[batch, steps] (bytes, NULL: all set): where 0, h_t = h_{t-1} and c_t = c_{t-1}.  h0, c0[batch, units]
+ * (NULL: zeros).  go_backwards != 0 walks time indices steps-1 .. 0.  out_seq[batch, steps, units] (optional) is in
+ * PROCESSING order: h_t, repeated at a masked step, zeros before a row's first unmasked step (Keras' rule).
+ * out_h, out_c[batch, units]: the last state.  The training forward also fills save_i / save_f / save_g / save_o /
+ * save_cprev / save_hprev [batch, steps, units], indexed by TIME index, masked steps included (all six or none).
+ *   bwd: dseq (processing order), dlast_h and dlast_c are the gradients of out_seq / out_h / out_c (each optional);
+ *     da[batch, steps, 4 units] = (da_i, da_f, da_c, da_o), the gradient of xproj AND of h_{t-1} @ recurrent_kernel:
+ *     d recurrent_kernel = save_hprev^T @ da; by time index, zeros at masked steps; dh0, dc0[batch, units].
+ * units <= TFRS_LSTM_MAX_UNITS (TFRS_ENOTIMPL above).  batch == 0 or steps == 0 returns without a launch.  No
+ * workspace, no atomics: results are identical from run to run.
+ * ------------------------------------------------------------------------- */
+#define TFRS_LSTM_MAX_UNITS 64
+int tfrs_lstm_fwd(const float *xproj, const float *recurrent_kernel, const uint8_t *mask, const float *h0,
+                  const float *c0, int64_t batch, int steps, int units, int go_backwards, float *out_seq,
+                  float *out_h, float *out_c, float *save_i, float *save_f, float *save_g, float *save_o,
+                  float *save_cprev, float *save_hprev, void *stream);
+int tfrs_lstm_bwd(const float *recurrent_kernel, const uint8_t *mask, const float *save_i, const float *save_f,
+                  const float *save_g, const float *save_o, const float *save_cprev, const float *dseq,
+                  const float *dlast_h, const float *dlast_c, int64_t batch, int steps, int units, int go_backwards,
+                  float *da, float *dh0, float *dc0, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Numeric preprocessing (layers/numeric.py; csrc/numeric.hip): the kernels behind Discretization and
  * Normalization.  Plain pointers, every launch on `stream`, no atomics, no host synchronisation, no allocation.  The
  * input x is f32, f64, int32 or int64 (TFRS_NUMERIC_*).  Bad arguments (a NULL pointer, a negative count, an unknown

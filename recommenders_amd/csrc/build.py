@@ -49,6 +49,7 @@ SOURCES = [
     "gemm16.hip",
     "scann.hip",
     "gru.hip",
+    "lstm.hip",
     "numeric.hip",
 ]
 
@@ -63,7 +64,10 @@ EXTRA_FLAGS = {"topk_scan16.hip": ["-fno-honor-nans"],
                # Normalization's forward is pinned bit for bit: f32 division and square root correctly rounded (hipcc's
                # default, stated here so that a changed default cannot change results) and no fused multiply-add formed
                # from the subtraction and division sequences
-               "numeric.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off"]}
+               "numeric.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off"],
+               # the gate and cell arithmetic stays scalar f32 (v_mul / v_fma per element): no packed-f32 pairs formed
+               # from neighbouring rows of a lane
+               "lstm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc() -> str:

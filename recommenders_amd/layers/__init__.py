@@ -7,4 +7,4 @@ from recommenders_amd.layers.preprocessing import IntegerLookup, StringLookup, T
 from recommenders_amd.layers import numeric  # noqa: F401
 from recommenders_amd.layers.numeric import Discretization, Normalization  # noqa: F401
 from recommenders_amd.layers.embedding import Embedding  # noqa: F401
-from recommenders_amd.layers.recurrent import GRU  # noqa: F401
+from recommenders_amd.layers.recurrent import GRU, LSTM  # noqa: F401
