@@ -1209,6 +1209,30 @@ int tfrs_lstm_bwd(const float *recurrent_kernel, const uint8_t *mask, const floa
                   float *da, float *dh0, float *dc0, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The core of a Keras MultiHeadAttention layer and its backward, ONE launch each (layers/attention.py,
+ * csrc/attention.hip).  Not the max-sim "multi-head" queries of the retrieval task (tfrs_*_mh_*).
+ *   q[B, Tq, H, dk], k[B, Tk, H, dk], v[B, Tk, H, dv], out[B, Tq, H, dv]: f32, row-major: the [B T, H d] outputs of
+ *   the projection GEMMs as they are.  attn_mask[B, Tq, Tk], q_mask[B, Tq], k_mask[B, Tk]: bytes, non-zero = attend,
+ *   each may be NULL.  causal != 0 keeps j <= i.  A pair (i, j) is allowed when every given mask allows it.
+ *   s_ij = scale (q_i . k_j);  p_i = softmax of s_i over the allowed j;  out_i = sum_j p_ij v_j;
+ *   lse[B, H, Tq] = the log-sum-exp of s_i over the allowed j.
+ * A query row with NO allowed key gives out_i = +0, lse_i = +inf and contributes zero to every gradient.
+ *   bwd: out and lse as the forward wrote them, dout[B, Tq, H, dv]; writes dq, dkey, dv_out in the layouts of q, k, v.
+ * Tq, Tk <= TFRS_ATTENTION_MAX_SEQ and dk, dv <= TFRS_ATTENTION_MAX_HEAD_DIM (TFRS_ENOTIMPL above, nothing launched,
+ * the message names the argument).  B == 0 or Tq == 0 returns TFRS_OK without a launch (the caller zeroes dkey and
+ * dv_out).  No workspace, no atomics: results are identical from run to run and independent of B.
+ * ------------------------------------------------------------------------- */
+#define TFRS_ATTENTION_MAX_SEQ 128
+#define TFRS_ATTENTION_MAX_HEAD_DIM 64
+int tfrs_attention_fwd(const float *q, const float *k, const float *v, const uint8_t *attn_mask,
+                       const uint8_t *q_mask, const uint8_t *k_mask, int64_t B, int Tq, int Tk, int H, int dk, int dv,
+                       float scale, int causal, float *out, float *lse, void *stream);
+int tfrs_attention_bwd(const float *q, const float *k, const float *v, const uint8_t *attn_mask,
+                       const uint8_t *q_mask, const uint8_t *k_mask, const float *out, const float *lse,
+                       const float *dout, int64_t B, int Tq, int Tk, int H, int dk, int dv, float scale, int causal,
+                       float *dq, float *dkey, float *dv_out, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Numeric preprocessing (layers/numeric.py; csrc/numeric.hip): the kernels behind Discretization and
  * Normalization.  Plain pointers, every launch on `stream`, no atomics, no host synchronisation, no allocation.  The
  * input x is f32, f64, int32 or int64 (TFRS_NUMERIC_*).  Bad arguments (a NULL pointer, a negative count, an unknown

@@ -190,6 +190,9 @@ SIGNATURES = {
     "tfrs_gru_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P]),
     "tfrs_lstm_fwd": (c_int, [P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
     "tfrs_lstm_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_i64, c_int, c_int, c_int, P, P, P, P]),
+    "tfrs_attention_fwd": (c_int, [P, P, P, P, P, P, c_i64, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P]),
+    "tfrs_attention_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_i64, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                   P, P, P, P]),
     "tfrs_bucketize": (c_int, [P, c_int, c_i64, P, c_i64, P, P]),
     "tfrs_normalize": (c_int, [P, c_int, c_i64, c_i64, P, P, c_int, P, P]),
     "tfrs_moments_workspace_bytes": (c_size_t, [c_i64, c_i64]),

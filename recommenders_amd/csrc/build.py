@@ -50,6 +50,7 @@ SOURCES = [
     "scann.hip",
     "gru.hip",
     "lstm.hip",
+    "attention.hip",
     "numeric.hip",
 ]
 

@@ -8,3 +8,4 @@ from recommenders_amd.layers import numeric  # noqa: F401
 from recommenders_amd.layers.numeric import Discretization, Normalization  # noqa: F401
 from recommenders_amd.layers.embedding import Embedding  # noqa: F401
 from recommenders_amd.layers.recurrent import GRU, LSTM  # noqa: F401
+from recommenders_amd.layers.attention import MultiHeadAttention  # noqa: F401
