@@ -1287,6 +1287,37 @@ int tfrs_moments_update(const void *x, int dtype, int64_t n_rows, int64_t f, dou
 int tfrs_moments_finalize(const double *state, int64_t f, float *mean, float *variance, float *scale, void *stream);
 int tfrs_moments_reset(double *state, int64_t f, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Layer normalisation over the last axis, with an optional fused residual add, and its backward
+ * (layers/layer_norm.py, csrc/layer_norm.hip).  Not the feature-wise Normalization above.
+ *   x[N, D], residual[N, D], y[N, D], sum_out[N, D], dy, dsum, dx[N, D]: f32, row-major, contiguous; gamma[D],
+ *   beta[D]; mean[N], rstd[N].  Every launch on `stream`; no atomics, no host synchronisation, no allocation.
+ *   fwd, ONE launch: s = x + residual (s = x with residual NULL); mean = sum(s) / D; var = sum((s - mean)^2) / D;
+ *     rstd = 1 / sqrt(var + eps), an IEEE square root and division; y = (s - mean) rstd gamma + beta.  gamma NULL is
+ *     ones, beta NULL is zeros.  sum_out (needs residual), mean and rstd may each be NULL and are then not written.
+ *   bwd, TWO launches (one when dgamma and dbeta are both NULL): x is what was normalised (the saved s of a fused
+ *     call), mean and rstd as the forward wrote them.  xhat = (x - mean) rstd; g = dy gamma;
+ *     dx = rstd (g - mean(g) - xhat mean(g xhat)) + dsum, dsum (the gradient that reached sum_out) may be NULL; dx is
+ *     the gradient of x and of residual alike.  dgamma[D] = sum_n dy xhat, dbeta[D] = sum_n dy; dx, dgamma and dbeta
+ *     may each be NULL (not all three).  With dgamma or dbeta the workspace holds one slab [2][D] per workgroup:
+ *     tfrs_layer_norm_workspace_bytes(N, D) bytes, 4-byte aligned.
+ * D <= TFRS_LAYER_NORM_MAX_DIM (TFRS_ENOTIMPL above, nothing launched, the message names D).  N == 0 returns TFRS_OK
+ * without a launch (the caller zeroes dgamma and dbeta).  NaN and Inf propagate as the arithmetic dictates.
+ * Alignment: with D % 4 == 0 and x, residual, gamma, beta, y, sum_out (bwd: x, gamma, dy, dsum, dx) all 16-byte
+ * aligned the kernels use 16-byte accesses, otherwise dword accesses with another (equally fixed) summation order;
+ * every pointer must be 4-byte aligned.  The grid is min(ceil(N / rows per workgroup), TFRS_LAYER_NORM_MAX_GROUPS), a
+ * function of (N, D) and never of the device, and every sum has a fixed order: results are identical from run to
+ * run, and a row's y and dx do not depend on N.
+ * ------------------------------------------------------------------------- */
+#define TFRS_LAYER_NORM_MAX_DIM 8192
+#define TFRS_LAYER_NORM_MAX_GROUPS 1024
+int tfrs_layer_norm_fwd(const float *x, const float *residual, const float *gamma, const float *beta, int64_t N,
+                        int64_t D, float eps, float *y, float *sum_out, float *mean, float *rstd, void *stream);
+size_t tfrs_layer_norm_workspace_bytes(int64_t N, int64_t D);
+int tfrs_layer_norm_bwd(const float *x, const float *mean, const float *rstd, const float *gamma, const float *dy,
+                        const float *dsum, int64_t N, int64_t D, float *dx, float *dgamma, float *dbeta,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,9 @@ SIGNATURES = {
     "tfrs_moments_update": (c_int, [P, c_int, c_i64, c_i64, P, P, c_size_t, P]),
     "tfrs_moments_finalize": (c_int, [P, c_i64, P, P, P, P]),
     "tfrs_moments_reset": (c_int, [P, c_i64, P]),
+    "tfrs_layer_norm_fwd": (c_int, [P, P, P, P, c_i64, c_i64, c_float, P, P, P, P, P]),
+    "tfrs_layer_norm_workspace_bytes": (c_size_t, [c_i64, c_i64]),
+    "tfrs_layer_norm_bwd": (c_int, [P, P, P, P, P, P, c_i64, c_i64, P, P, P, P, c_size_t, P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -52,6 +52,7 @@ SOURCES = [
     "lstm.hip",
     "attention.hip",
     "numeric.hip",
+    "layer_norm.hip",
 ]
 
 
@@ -66,6 +67,8 @@ EXTRA_FLAGS = {"topk_scan16.hip": ["-fno-honor-nans"],
                # default, stated here so that a changed default cannot change results) and no fused multiply-add formed
                # from the subtraction and division sequences
                "numeric.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off"],
+               # rstd = 1 / sqrt(var + eps) with the IEEE square root and division (stated for the same reason)
+               "layer_norm.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"],
                # the gate and cell arithmetic stays scalar f32 (v_mul / v_fma per element): no packed-f32 pairs formed
                # from neighbouring rows of a lane
                "lstm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}

@@ -9,3 +9,4 @@ from recommenders_amd.layers.numeric import Discretization, Normalization  # noq
 from recommenders_amd.layers.embedding import Embedding  # noqa: F401
 from recommenders_amd.layers.recurrent import GRU, LSTM  # noqa: F401
 from recommenders_amd.layers.attention import MultiHeadAttention  # noqa: F401
+from recommenders_amd.layers.layer_norm import LayerNormalization  # noqa: F401
